@@ -2,7 +2,16 @@
 """Throughput of the MI355X codon-LM training step (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3|c5] [--path engine|trainer]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the
+legs that take runs of their own: the per-kernel probe passes and the live roofline window
+(`kernels`, `roofline`; off with --no-kernel-roofline) and the fp32 CPU baseline (`cpu_baseline`;
+off with --no-cpu-baseline).  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32): the loss, and the parameters and gradients it left (the eval forward:
+its logits) -- an array above DUMP_SAMPLE elements as a fixed seeded sample.  Inputs, weights
+and dropout seeds depend on the arguments only, so two builds compare output for output.
 
 Workload = BASELINE config C4: TinyGPT 12L8H d512 (hd 64), T=1024, V=68 codons, GELU MLP,
 SEP-segment causal mask, dropout 0.1, label smoothing 0.05, bf16 compute with fp32
@@ -56,6 +65,24 @@ CONFIGS = {
 CPU_BATCH = {"c4": 2, "c2": 4, "c3": 4, "c5": 4}
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, chip table)
 PEAK_HBM_GBS = 8000.0
+DUMP_SAMPLE = 4 << 20   # --dump-outputs: elements kept of a larger array (3 arrays x 16 MiB at most)
+
+
+def _dump_array(t):
+    """float32 host copy of a device tensor, flattened; above DUMP_SAMPLE elements the fixed
+    seeded sample of it (sorted positions drawn once from default_rng(1337))."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(1337).integers(0, flat.numel(), size=DUMP_SAMPLE))
+        flat = flat[torch.from_numpy(pos).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, arrays):
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(out_dir / f"{name}.npy", _dump_array(t))
 
 
 def flops_per_token(c, V=68):
@@ -166,13 +193,20 @@ def main():
                          "forward: the eval-mode batched forward of extract_embeddings / query_model")
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: kernel probe passes + live roofline "
+                         "window, and the fp32 CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-roofline", action="store_true", help="with --full: skip the kernel probes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--attn-bwd", default="auto", choices=["auto", "split", "fused"],
                     help="bf16 attention backward (cg_model_opts.attn_bwd_algo; A/B runs, default automatic)")
     ap.add_argument("--engine-opt", action="append", default=[], metavar="NAME=VALUE",
                     help="a cg_model_opts field for A/B runs (repeatable; all zero = the measured defaults)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -240,6 +274,7 @@ def main():
         return total
 
     fwd_only = args.path == "forward"
+    last = {}  # the eval forward's logits of the latest step (--dump-outputs)
     if fwd_only:
         model.eval()
 
@@ -247,6 +282,7 @@ def main():
             xb, _ = batches[i % nbuf]
             with torch.no_grad():
                 logits, _ = model(xb)
+            last["logits"] = logits
             return logits[:1, :1].float().sum()
     elif args.path == "engine" and not aux:
         def run(i):
@@ -293,7 +329,7 @@ def main():
     from codonlm_amd import _lib as L
     probes = {}
     dominant = 0
-    if not args.no_kernel_roofline and args.dtype == "bf16":
+    if args.full and not args.no_kernel_roofline and args.dtype == "bf16":
         nxt = args.warmup
         for kind in (L.PROBE_GEMM_PERS, L.PROBE_GEMM_DW_GROUPED, L.PROBE_GEMM_DW, L.PROBE_GEMM_FWD, L.PROBE_GEMM_DX,
                      L.PROBE_ATTN_FWD, L.PROBE_ATTN_DQ, L.PROBE_ATTN_DKDV, L.PROBE_ATTN_BWD, L.PROBE_DW_SLAB):
@@ -318,6 +354,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before the probe window below runs further steps
+        if fwd_only:
+            dump_outputs(args.dump_outputs, {"logits": last["logits"]})
+        else:
+            dump_outputs(args.dump_outputs, {"loss": loss, "params": model.flat_parameters(),
+                                             "grads": model.flat_grads()})
     # The timed region above carries no probe.  The roofline kernel is then timed live in a
     # separate window of `probe_steps` further steps: HIP events on the launch stream around 1
     # launch in `every` of that class -- the smallest every >= 4 coprime to the class's launches
@@ -435,7 +477,7 @@ def main():
                 ent.update({"tflops": round(v[0] / (v[1] * 1e-3) / 1e12, 1) if v[1] > 0 else None,
                             "frac": round(v[0] / (v[1] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if v[1] > 0 else None})
             result["kernels"][L.PROBE_NAMES[kk]] = ent
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.config, c)
         # the two sides run different batches (the CPU at the reference's default per-device batch, the
         # GPU at one optimizer step's sequences as one microbatch): both stated, so the ratio is read

@@ -297,10 +297,25 @@ def data_order_case():
     print("[golden] data_order")
 
 
+def init_case():
+    """The reference TinyGPT's state_dict as its constructor leaves it after torch.manual_seed(11)
+    (GQA + RoPE + SwiGLU, 2L4H d64 T32): the initial weights a drop-in must reproduce bit for bit."""
+    kw = dict(n_layer=2, n_head=4, n_embd=64, n_kv_head=2, use_swiglu=True, use_rope=True)
+    torch.manual_seed(11)
+    ref = TinyGPT(68, 32, **kw)
+    out = {"config": np.array(json.dumps(dict(vocab_size=68, block_size=32, seed=11, **kw)))}
+    for k, v in ref.state_dict().items():
+        out[f"state/{k}"] = v.detach().numpy().copy()
+    np.savez_compressed(HERE / "init_seed11.npz", **out)
+    print(f"[golden] init_seed11: {len(out) - 1} tensors")
+
+
 def main():
     torch.set_num_threads(8)
     only = set(sys.argv[1:])
     if only:  # regenerate selected fixtures only, e.g. `make_golden.py aux_objective`
+        if "init_seed11" in only:
+            init_case()
         if "aux_objective" in only:
             aux_objective_case()
         if "data_order" in only:
@@ -333,6 +348,7 @@ def main():
     objectives_case()
     aux_objective_case()
     data_order_case()
+    init_case()
 
 
 if __name__ == "__main__":

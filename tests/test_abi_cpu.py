@@ -89,25 +89,19 @@ def test_state_dict_and_init_match_reference_layout(kw):
         assert p.grad is not None and p.grad.shape == p.shape
 
 
-def test_reference_init_bitwise(tmp_path):
-    import sys
-    ref = Path("/root/reference")
-    if not ref.exists():
-        pytest.skip("reference tree only present in the build container")
-    sys.path.insert(0, str(ref))
-    try:
-        from src.codonlm.model_tiny_gpt import TinyGPT as Ref
-    except Exception as e:  # pragma: no cover
-        pytest.skip(f"reference not importable: {e}")
-    finally:
-        sys.path.remove(str(ref))
+def test_reference_init_bitwise(golden):
+    """torch.manual_seed(11) gives the reference TinyGPT's initial state_dict bit for bit
+    (golden init_seed11.npz: the reference constructor's own output, tests/golden/make_golden.py)."""
+    cfg, ref = golden("init_seed11")
     from codonlm_amd import TinyGPT
-    torch.manual_seed(11)
-    r = Ref(68, 32, n_layer=2, n_head=4, n_embd=64, n_kv_head=2, use_swiglu=True, use_rope=True)
-    torch.manual_seed(11)
-    m = TinyGPT(68, 32, n_layer=2, n_head=4, n_embd=64, n_kv_head=2, use_swiglu=True, use_rope=True, device="cpu")
-    for k, v in r.state_dict().items():
-        assert torch.equal(v, m.state_dict()[k]), k
+    assert (cfg.pop("vocab_size"), cfg.pop("block_size")) == (68, 32)
+    torch.manual_seed(cfg.pop("seed"))
+    m = TinyGPT(68, 32, device="cpu", **cfg)
+    sd = m.state_dict()
+    state = {k[len("state/"):]: torch.from_numpy(v) for k, v in ref.items() if k.startswith("state/")}
+    assert len(state) >= 20 and "tok_emb.weight" in state
+    for k, v in state.items():
+        assert v.dtype == sd[k].dtype and torch.equal(v, sd[k]), k
 
 
 def test_workspace_and_layout_sizes():

@@ -7,7 +7,7 @@ cfg=${1:-c4}; shift || true
 O=gpurun_out/${ROUND:-r3}_$cfg
 mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py --config $cfg "$@" > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 300 python bench.py --full --config $cfg "$@" > $O/bench.json 2> $O/bench.err &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- \
   python bench.py --config $cfg --no-cpu-baseline --no-kernel-roofline --steps 20 --warmup 5 "$@" > $O/trace.log 2>&1 &&
 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o run --output-format csv -- \

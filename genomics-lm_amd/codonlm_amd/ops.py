@@ -266,14 +266,21 @@ def attn_bwd(qkv, segstart, y, dy, lse, B, T, H, KV, hd, window=0, drop_seed=0, 
     return dqkv
 
 
-def cross_entropy(logits, targets, eps=0.0, weight=None, ignore_index=0, grad_dtype=torch.float32, pad_to=None):
+def cross_entropy(logits, targets, eps=0.0, weight=None, ignore_index=0, grad_dtype=torch.float32, pad_to=None,
+                  grad_scale=1.0, split=False):
+    """(loss, dlogits [rows][pad_to or V]); the gradient is multiplied by grad_scale, the loss is not.
+    split (CG_BF16X2): dlogits is bf16 [rows][pad_to], hi = bf16(g) at column c and lo = bf16(g - hi)
+    at column pad_to/2 + c (pad_to even, pad_to/2 >= V)."""
     rows, V = logits.shape
     ldd = pad_to or V
+    if split:
+        grad_dtype = torch.bfloat16
     dl = torch.empty(rows, ldd, dtype=grad_dtype, device=logits.device)
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
     ws = torch.empty(int(L.lib.cg_ce_workspace(rows)) // 4 + 1, dtype=torch.float32, device=logits.device)
     L.check(L.lib.cg_cross_entropy(logits.data_ptr(), logits.stride(0), targets.contiguous().data_ptr(), rows, V,
-                                   float(eps), _p(weight), int(ignore_index), 1.0, _dt(dl), dl.data_ptr(), ldd,
+                                   float(eps), _p(weight), int(ignore_index), float(grad_scale),
+                                   L.CG_BF16X2 if split else _dt(dl), dl.data_ptr(), ldd,
                                    loss.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr(logits.device)),
             "cg_cross_entropy")
     return loss, dl
@@ -298,14 +305,122 @@ def cast_to_bf16(x):
     return out.view(x.shape)
 
 
-def cast_pad_2d(src, dcols, dtype=torch.bfloat16):
-    """fp32 [rows][cols] -> dtype [rows][dcols], pad columns zero."""
+def cast_from_bf16(x):
+    """bf16 -> fp32 (exact), any shape."""
+    L.require_device(x, "cast_from_bf16")
+    if x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError("cast_from_bf16 takes a contiguous bf16 tensor")
+    out = torch.empty(x.numel(), dtype=torch.float32, device=x.device)
+    L.check(L.lib.cg_cast_bf16_to_f32(x.data_ptr(), out.data_ptr(), x.numel(), L.stream_ptr(x.device)),
+            "cg_cast_bf16_to_f32")
+    return out.view(x.shape)
+
+
+def cast_pad_2d(src, dcols, dtype=torch.bfloat16, out=None, split=False):
+    """fp32 [rows][cols] -> dtype [rows][dcols], pad columns zero.  split (CG_BF16X2): bf16
+    [rows][2 dcols], hi = bf16(v) at column c and lo = bf16(v - hi) at column dcols + c.
+    out (optional): the destination, a row-major view at least that wide (its row stride is used)."""
     L.require_device(src, "cast_pad_2d")
     rows, cols = src.shape
-    out = torch.empty(rows, dcols, dtype=dtype, device=src.device)
-    L.check(L.lib.cg_cast_pad_2d(src.data_ptr(), src.stride(0), rows, cols, _dt(out), out.data_ptr(), out.stride(0),
-                                 dcols, L.stream_ptr(src.device)), "cg_cast_pad_2d")
+    if split:
+        dtype = torch.bfloat16
+    if out is None:
+        out = torch.empty(rows, 2 * dcols if split else dcols, dtype=dtype, device=src.device)
+    elif out.dtype != dtype or out.dim() != 2 or out.shape[0] != rows or out.stride(1) != 1:
+        raise ValueError("cast_pad_2d: out must be a row-major [rows][*] view of the destination dtype")
+    L.check(L.lib.cg_cast_pad_2d(src.data_ptr(), src.stride(0), rows, cols, L.CG_BF16X2 if split else _dt(out),
+                                 out.data_ptr(), out.stride(0), dcols, L.stream_ptr(src.device)), "cg_cast_pad_2d")
     return out
+
+
+def scale_dev_(x, scale, cols=None, split=False):
+    """In-place x[:, :cols] *= scale[()] with the scale read on the device (fp32 scalar tensor).
+    x: row-major 2-D fp32 / bf16 view (row stride = ld).  split (CG_BF16X2): bf16 rows holding
+    hi in [0, ld/2) and lo in [ld/2, ld); the pair sum is scaled and split again."""
+    L.require_device(x, "scale_dev_")
+    L.require_device(scale, "scale_dev_")
+    if x.dim() != 2 or x.stride(1) != 1 or scale.dtype != torch.float32:
+        raise ValueError("scale_dev_: row-major 2-D x and an fp32 device scalar")
+    rows = x.shape[0]
+    if cols is None:
+        cols = x.shape[1] // 2 if split else x.shape[1]
+    L.check(L.lib.cg_scale_dev(L.CG_BF16X2 if split else _dt(x), x.data_ptr(), x.stride(0), rows, int(cols),
+                               scale.data_ptr(), L.stream_ptr(x.device)), "cg_scale_dev")
+    return x
+
+
+def nonfinite_flag(x, flag=None):
+    """flag (int32 device scalar, created zero when None) |= any(!isfinite(x)) over a contiguous fp32 x."""
+    L.require_device(x, "nonfinite_flag")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("nonfinite_flag takes a contiguous fp32 tensor")
+    if flag is None:
+        flag = torch.zeros((), dtype=torch.int32, device=x.device)
+    L.check(L.lib.cg_nonfinite_flag(x.data_ptr(), x.numel(), flag.data_ptr(), L.stream_ptr(x.device)),
+            "cg_nonfinite_flag")
+    return flag
+
+
+def embed_fwd(idx, tok_emb, pos_emb=None, drop_seed=0, drop_p=0.0, out=None):
+    """x[b*T + t] = dropout(tok_emb[idx[b, t]] (+ pos_emb[t])) as fp32 [B*T][d] (keep bits
+    cg_keep(seed, row, column)).  out (optional): a contiguous fp32 [B*T][d] destination."""
+    L.require_device(idx, "embed_fwd")
+    L.require_device(tok_emb, "embed_fwd")
+    B, T = idx.shape
+    d = tok_emb.shape[1]
+    if idx.dtype != torch.int64 or tok_emb.dtype != torch.float32 or not tok_emb.is_contiguous():
+        raise ValueError("embed_fwd: int64 ids and a contiguous fp32 table")
+    if pos_emb is not None and (pos_emb.dtype != torch.float32 or not pos_emb.is_contiguous()
+                                or pos_emb.shape[0] < T or pos_emb.shape[1] != d):
+        raise ValueError("embed_fwd: pos_emb must be a contiguous fp32 [>= T][d]")
+    if out is None:
+        out = torch.empty(B * T, d, dtype=torch.float32, device=tok_emb.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B * T, d) or not out.is_contiguous():
+        raise ValueError("embed_fwd: out must be a contiguous fp32 [B*T][d]")
+    L.check(L.lib.cg_embed_fwd(idx.contiguous().data_ptr(), tok_emb.data_ptr(), _p(pos_emb), out.data_ptr(), B, T, d,
+                               int(drop_seed) & 0xFFFFFFFF, float(drop_p), L.stream_ptr(tok_emb.device)),
+            "cg_embed_fwd")
+    return out
+
+
+def attn_decode(q, cache, pos, H, KV, hd, segstate=None, window=0, Tmax=None):
+    """One-token attention over a KV cache: q [B][>= H hd], cache [B][Tmax][ldc] (K head kvh at
+    column kvh hd, V at KV hd + kvh hd); the query of position `pos` sees keys lo..pos, lo =
+    segstate[b] (int32 [B], None = 0) raised to pos - window + 1 with a window -> y [B][H hd]."""
+    L.require_device(q, "attn_decode")
+    L.require_device(cache, "attn_decode")
+    if q.dtype != cache.dtype or cache.dim() != 3 or cache.stride(2) != 1 or q.stride(1) != 1:
+        raise ValueError("attn_decode: q and cache share a dtype; cache is [B][Tmax][ldc]")
+    B = q.shape[0]
+    if Tmax is None:
+        Tmax = cache.shape[1]
+    if cache.shape[0] != B or cache.stride(0) != Tmax * cache.stride(1):
+        raise ValueError("attn_decode: cache rows of one sequence must be Tmax consecutive rows")
+    y = torch.empty(B, H * hd, dtype=q.dtype, device=q.device)
+    L.check(L.lib.cg_attn_decode(_dt(q), q.data_ptr(), q.stride(0), cache.data_ptr(), cache.stride(1), int(Tmax),
+                                 int(pos), _p(segstate), int(window or 0), B, H, KV, hd, y.data_ptr(), y.stride(0),
+                                 L.stream_ptr(q.device)), "cg_attn_decode")
+    return y
+
+
+def attn_probs(qkv, segstart, lse, B, T, H, KV, hd, window=0):
+    """softmax(QK^T / sqrt(hd)) on the visible (query, key) pairs from the forward's qkv rows and
+    LSE, 0 elsewhere: fp32 [B][H][T][T]."""
+    L.require_device(qkv, "attn_probs")
+    out = torch.empty(B, H, T, T, dtype=torch.float32, device=qkv.device)
+    L.check(L.lib.cg_attn_probs(_dt(qkv), qkv.data_ptr(), qkv.stride(0), _p(segstart), lse.data_ptr(), out.data_ptr(),
+                                B, T, H, KV, hd, int(window or 0), L.stream_ptr(qkv.device)), "cg_attn_probs")
+    return out
+
+
+def segstate_step(tok, sep_id, pos, segstate):
+    """In place: segstate[b] = pos where tok[b] == sep_id (sep_id None / negative: untouched)."""
+    L.require_device(tok, "segstate_step")
+    if tok.dtype != torch.int64 or segstate.dtype != torch.int32 or tok.numel() != segstate.numel():
+        raise ValueError("segstate_step: int64 tokens [B], int32 state [B]")
+    L.check(L.lib.cg_segstate_step(tok.contiguous().data_ptr(), tok.numel(), -1 if sep_id is None else int(sep_id),
+                                   int(pos), segstate.data_ptr(), L.stream_ptr(tok.device)), "cg_segstate_step")
+    return segstate
 
 
 def _ids(values):

@@ -134,6 +134,29 @@ class Model(C.Structure):
                 ("reduce_pending", ReduceBatch)]
 
 
+# cg_sample_step: token classes, sequence flags, parameters and the per-sequence state
+TOK_CODON, TOK_STOP, TOK_EOS = 1, 2, 4
+(GEN_DONE, GEN_TERMINAL_STOP, GEN_EARLY_STOP, GEN_EOS, GEN_TARGET, GEN_CAP, GEN_CONTEXT_FULL) = (1, 2, 4, 8, 16, 32, 64)
+INT_MAX = 2 ** 31 - 1
+
+
+class SampleParams(C.Structure):
+    _fields_ = [("V", i32), ("tok_class", vp), ("allowed", vp), ("temperature", f32), ("topk", i32),
+                ("target_codons", i32), ("max_codons", i32), ("max_tokens", i32),
+                ("require_terminal_stop", i32), ("stop_on_eos", i32), ("stop_on_bio_stop", i32),
+                ("stop_bias", f32), ("trigger_class_max", i32), ("bias_window", i32), ("n_term_classes", i32),
+                ("seed", u32), ("Tmax", i32)]
+
+
+class GenState(C.Structure):
+    _fields_ = [("pos0", C.c_int32), ("pos", C.c_int32), ("n_tokens", C.c_int32), ("n_codons", C.c_int32),
+                ("flags", C.c_int32), ("bias_steps", C.c_int32), ("last_term_class", C.c_int32),
+                ("stream", u32)]
+
+
+GEN_STATE_FIELDS = tuple(f for f, _ in GenState._fields_)  # the int32 columns of a (B, 8) state tensor
+
+
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {
     "cg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -202,6 +225,18 @@ SIGNATURES = {
     "cg_model_decode": (i32, [C.POINTER(Model), vp, i32, i32, vp, i32, vp, vp, sz, vp, vp]),
     "cg_attn_decode": (i32, [i32, vp, i64, vp, i64, i32, i32, vp, i32, i32, i32, i32, i32, vp, i64, vp]),
     "cg_segstate_step": (i32, [vp, i32, i32, i32, vp, vp]),
+    "cg_decode_ragged_workspace_bytes": (sz, [C.POINTER(ModelCfg), i32]),
+    "cg_model_prefill_ragged": (i32, [C.POINTER(Model), vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "cg_model_decode_ragged": (i32, [C.POINTER(Model), vp, vp, i32, vp, i32, vp, vp, sz, vp, vp, i64, vp]),
+    "cg_attn_decode_ragged": (i32, [i32, vp, i64, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]),
+    "cg_embed_fwd_pos": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "cg_rope_pos": (i32, [i32, vp, i64, vp, i32, i32, i32, i32, vp, vp, i32, vp]),
+    "cg_kv_append": (i32, [i32, vp, i64, vp, i64, i32, vp, i32, i32, vp]),
+    "cg_kv_scatter": (i32, [i32, vp, i64, i32, vp, i64, i32, vp, i32, i32, vp]),
+    "cg_segstate_step_ragged": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "cg_gather_rows": (i32, [vp, i64, vp, i32, i32, vp, i64, i32, vp, vp, i32, vp]),
+    "cg_row_head": (i32, [i32, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
+    "cg_sample_step": (i32, [C.POINTER(SampleParams), vp, i64, vp, i64, vp, vp, vp, i64, vp, i32, vp]),
     "cg_model_hidden": (vp, [C.POINTER(Model), i32, C.POINTER(i32), C.POINTER(i64)]),
     "cg_model_attn_probs": (i32, [C.POINTER(Model), i32, vp, vp]),
     "cg_probe_enable": (i32, [i32]),

@@ -244,6 +244,9 @@ class Engine:
     def new_kv_cache(self, B: int, Tmax: int | None = None) -> "KVCache":
         return KVCache(self, B, Tmax or self.cfg.block_size)
 
+    def new_ragged_kv_cache(self, B: int, Tmax: int | None = None) -> "RaggedKVCache":
+        return RaggedKVCache(self, B, Tmax or self.cfg.block_size)
+
     def backward_phase(self, phase: int, layer: int = 0, accumulate: bool = False):
         st = L.stream_ptr(self.flat.device)
         L.check(L.lib.cg_model_backward(C.byref(self.model), phase, layer, int(bool(accumulate)), st),
@@ -345,3 +348,78 @@ class KVCache:
         self._tok = tok
         self.pos += 1
         return logits
+
+
+class RaggedKVCache:
+    """The KV cache of a batch whose sequences sit at different positions (cg_model_prefill_ragged /
+    cg_model_decode_ragged): one prefill of right-padded prompts, then one native call per step
+    with the positions in a device int32 tensor.  A row whose position is negative (or >= Tmax)
+    is inactive in that step: its cache rows, ``logits`` row and ``term`` row stay as they are.
+    ``logits`` (B, V) and ``term`` (B, n_classes; models with a termination head) are fixed
+    buffers every step writes in place, so a generation loop holds no per-step allocations."""
+
+    def __init__(self, engine: Engine, B: int, Tmax: int):
+        cfg = engine.cfg
+        if Tmax > cfg.block_size:
+            raise ValueError("Tmax exceeds block_size")
+        self.eng, self.B, self.Tmax = engine, int(B), int(Tmax)
+        dev = engine.flat.device
+        nbytes = int(L.lib.cg_kv_cache_bytes(C.byref(engine.model.cfg), self.B, self.Tmax))
+        self.cache = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        self.seg = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        wsb = int(L.lib.cg_decode_ragged_workspace_bytes(C.byref(engine.model.cfg), self.B))
+        self.ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
+        self.logits = torch.zeros(self.B, cfg.vocab_size, dtype=torch.float32, device=dev)
+        self.term = (torch.zeros(self.B, cfg.termination_n_classes, dtype=torch.float32, device=dev)
+                     if cfg.termination_aux else None)
+
+    @torch.no_grad()
+    def prefill(self, idx: torch.Tensor, lens: torch.Tensor, window: int | None = None, *,
+                want_term: bool = False) -> torch.Tensor:
+        """Eval forward of the right-padded prompts (B, T) with lengths ``lens`` (B,) in 1..T;
+        returns ``logits``: row b holds the logits after prompt b's last token.  ``want_term``
+        also fills ``term`` with the termination head at that row."""
+        eng = self.eng
+        L.require_device(idx, "RaggedKVCache.prefill")
+        B, T = idx.shape
+        if B != self.B or T > self.Tmax:
+            raise ValueError(f"prompts {tuple(idx.shape)} do not fit the cache (B={self.B}, Tmax={self.Tmax})")
+        dev = self.cache.device
+        idx = idx.to(device=dev, dtype=torch.int64).contiguous()
+        lens = lens.reshape(B).to(device=dev, dtype=torch.int32).contiguous()
+        eng._ensure_workspace(B, T)
+        eng.sync_shadow()
+        eng._idx, eng._targets = idx, None
+        L.check(L.lib.cg_model_prefill_ragged(C.byref(eng.model), idx.data_ptr(), lens.data_ptr(), B, T,
+                                              int(window or 0), self.cache.data_ptr(), self.Tmax,
+                                              self.seg.data_ptr(), self.logits.data_ptr(), L.stream_ptr(dev)),
+                "cg_model_prefill_ragged")
+        if want_term:
+            if self.term is None:
+                raise ValueError("the model has no termination head")
+            term, _ = eng.aux_forward()
+            rows = torch.arange(B, device=dev) * T + (lens.to(torch.int64) - 1)
+            self.term.copy_(term[rows])
+        return self.logits
+
+    @torch.no_grad()
+    def decode(self, tok: torch.Tensor, pos: torch.Tensor, *, want_term: bool = False) -> torch.Tensor:
+        """Token tok[b] (int64, device) enters at cache row pos[b] (int32, device); returns
+        ``logits``, updated in the active rows."""
+        eng = self.eng
+        if tok.dtype != torch.int64 or pos.dtype != torch.int32 or tok.numel() != self.B or pos.numel() != self.B:
+            raise ValueError("tok must be int64 (B,) and pos int32 (B,)")
+        if not (tok.is_contiguous() and pos.is_contiguous()):
+            raise ValueError("tok and pos must be contiguous")
+        L.require_device(tok, "RaggedKVCache.decode")
+        L.require_device(pos, "RaggedKVCache.decode")
+        if want_term and self.term is None:
+            raise ValueError("the model has no termination head")
+        eng.sync_shadow()
+        L.check(L.lib.cg_model_decode_ragged(C.byref(eng.model), tok.data_ptr(), pos.data_ptr(), self.B,
+                                             self.cache.data_ptr(), self.Tmax, self.seg.data_ptr(),
+                                             self.ws.data_ptr(), self.ws.numel(), self.logits.data_ptr(),
+                                             self.term.data_ptr() if want_term else None,
+                                             self.term.stride(0) if want_term else 0,
+                                             L.stream_ptr(self.cache.device)), "cg_model_decode_ragged")
+        return self.logits

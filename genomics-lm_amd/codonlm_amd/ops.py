@@ -403,6 +403,44 @@ def attn_decode(q, cache, pos, H, KV, hd, segstate=None, window=0, Tmax=None):
     return y
 
 
+def attn_decode_ragged(q, cache, pos, H, KV, hd, segstate=None, window=0, Tmax=None, out=None):
+    """cg_attn_decode_ragged: attn_decode with one position per sequence, pos int32 [B] on the
+    device; rows with pos < 0 or >= Tmax are inactive and keep their row of ``out`` (zeros when
+    ``out`` is not given)."""
+    L.require_device(q, "attn_decode_ragged")
+    L.require_device(cache, "attn_decode_ragged")
+    L.require_device(pos, "attn_decode_ragged")
+    if q.dtype != cache.dtype or cache.dim() != 3 or cache.stride(2) != 1 or q.stride(1) != 1:
+        raise ValueError("attn_decode_ragged: q and cache share a dtype; cache is [B][Tmax][ldc]")
+    B = q.shape[0]
+    if Tmax is None:
+        Tmax = cache.shape[1]
+    if cache.shape[0] != B or cache.stride(0) != Tmax * cache.stride(1):
+        raise ValueError("attn_decode_ragged: cache rows of one sequence must be Tmax consecutive rows")
+    if pos.dtype != torch.int32 or pos.numel() != B or not pos.is_contiguous():
+        raise ValueError("attn_decode_ragged: pos is a contiguous int32 [B]")
+    y = out if out is not None else torch.zeros(B, H * hd, dtype=q.dtype, device=q.device)
+    L.check(L.lib.cg_attn_decode_ragged(_dt(q), q.data_ptr(), q.stride(0), cache.data_ptr(), cache.stride(1),
+                                        int(Tmax), pos.data_ptr(), _p(segstate), int(window or 0), B, H, KV, hd,
+                                        y.data_ptr(), y.stride(0), L.stream_ptr(q.device)), "cg_attn_decode_ragged")
+    return y
+
+
+def sample_step(params, logits, state, next_tok, out_ids, n_active=None, term_logits=None):
+    """cg_sample_step in place: ``params`` a _lib.SampleParams, logits fp32 [B][V], state int32 [B][8]
+    (cg_gen_state rows), next_tok int64 [B], out_ids int64 [B][cap], n_active int32 [1]."""
+    for t in (logits, state, next_tok, out_ids):
+        L.require_device(t, "sample_step")
+    B = logits.shape[0]
+    if (logits.dtype != torch.float32 or state.dtype != torch.int32 or tuple(state.shape) != (B, 8)
+            or not state.is_contiguous() or next_tok.dtype != torch.int64 or out_ids.dtype != torch.int64):
+        raise ValueError("sample_step: logits fp32 [B][V], state int32 [B][8], next_tok / out_ids int64")
+    L.check(L.lib.cg_sample_step(C.byref(params), logits.data_ptr(), logits.stride(0), _p(term_logits),
+                                 term_logits.stride(0) if term_logits is not None else 0, state.data_ptr(),
+                                 next_tok.data_ptr(), out_ids.data_ptr(), out_ids.stride(0), _p(n_active), B,
+                                 L.stream_ptr(logits.device)), "cg_sample_step")
+
+
 def attn_probs(qkv, segstart, lse, B, T, H, KV, hd, window=0):
     """softmax(QK^T / sqrt(hd)) on the visible (query, key) pairs from the forward's qkv rows and
     LSE, 0 elsewhere: fp32 [B][H][T][T]."""

@@ -1468,6 +1468,112 @@ extern "C" int cg_model_decode(cg_model* m, const int64_t* tok, int B, int pos, 
   return CG_OK;
 }
 
+// ===========================================================================
+// Ragged decoding: every sequence at its own device-side position (batched generation)
+// ===========================================================================
+namespace {
+size_t carve_dec_ragged(const cg_model_cfg* c, const Dims& D, int B, char* base, DecWS& W, float*& lg) {
+  const size_t off = carve_dec(c, D, B, base, W);  // (ends on the decode workspace's 256-byte pad)
+  WS w{base, off};
+  lg = w.take<float>((size_t)B * D.V * 4);  // the head product of all rows; the active ones are copied out
+  return w.off + 256;
+}
+}  // namespace
+
+extern "C" size_t cg_decode_ragged_workspace_bytes(const cg_model_cfg* cfg, int B) {
+  Dims D;
+  if (!dims_of(cfg, D) || B <= 0) return 0;
+  DecWS W;
+  float* lg;
+  return carve_dec_ragged(cfg, D, B, nullptr, W, lg);
+}
+
+extern "C" int cg_model_prefill_ragged(cg_model* m, const int64_t* idx, const int32_t* len, int B, int T, int window,
+                                       void* cache, int Tmax, int32_t* segstate, float* last_logits, void* stream) {
+  if (!m || !idx || !len || !cache || !segstate || !last_logits || B <= 0 || T <= 0 || Tmax < T ||
+      Tmax > m->cfg.block_size)
+    return CG_EINVAL;
+  CK(cg_model_forward(m, idx, nullptr, B, T, 0, 0, window, nullptr, nullptr, stream));
+  Ctx C;
+  CK(make_ctx(m, B, T, stream, C));
+  const Dims& D = C.D;
+  const size_t es = C.dt == CG_BF16 ? 2 : 4;
+  const size_t row = (size_t)2 * D.kvd * es;
+  // the [k|v] columns of the qkv rows t < len[b] (post-RoPE K) -> cache rows, one launch per layer
+  for (int l = 0; l < D.L; ++l)
+    CK(cg_kv_scatter(C.dt, (const char*)C.A.la[l].qkv + (size_t)D.d * es, D.Nqkv, T,
+                     (char*)cache + (size_t)l * B * Tmax * row, 2 * D.kvd, Tmax, len, B, 2 * D.kvd, C.s));
+  return cg_gather_rows(C.A.logits_pad, D.Vp, len, T, Tmax, last_logits, D.V, D.V,
+                        m->cfg.sep_id >= 0 ? C.A.seg : nullptr, segstate, B, C.s);
+}
+
+extern "C" int cg_model_decode_ragged(cg_model* m, const int64_t* tok, const int32_t* pos, int B, void* cache,
+                                      int Tmax, int32_t* segstate, void* dec_ws, size_t dec_ws_bytes, float* logits,
+                                      float* term_logits, long long ld_term, void* stream) {
+  if (!m || !tok || !pos || !cache || !segstate || !dec_ws || !logits || B <= 0) return CG_EINVAL;
+  if (Tmax <= 0 || Tmax > m->cfg.block_size) return CG_EINVAL;
+  if (m->cfg.dtype == CG_BF16 && !m->shadow) return CG_EINVAL;
+  if (m->cfg.use_rope && (!m->rope_cos || !m->rope_sin)) return CG_EINVAL;
+  const int nc = m->cfg.termination_aux ? m->cfg.termination_n_classes : 0;
+  if (term_logits && (nc <= 0 || ld_term < nc)) return CG_EINVAL;
+  Ctx C;
+  CK(make_dec_ctx(m, B, stream, C));
+  const Dims& D = C.D;
+  DecWS W;
+  float* lg;
+  if (carve_dec_ragged(&m->cfg, D, B, nullptr, W, lg) > dec_ws_bytes) return CG_EINVAL;
+  carve_dec_ragged(&m->cfg, D, B, (char*)dec_ws, W, lg);
+  const int d = D.d;
+  const float eps = m->cfg.ln_eps > 0 ? m->cfg.ln_eps : 1e-5f;
+  const size_t es = C.dt == CG_BF16 ? 2 : 4;
+  const size_t row = (size_t)2 * D.kvd * es;
+  CK(cg_embed_fwd_pos(tok, P(C, C.Lo.tok), C.Lo.pos >= 0 ? P(C, C.Lo.pos) : nullptr, pos, W.x, B, d, D.V, Tmax, C.s));
+  CK(cg_segstate_step_ragged(tok, pos, B, m->cfg.sep_id, Tmax, segstate, C.s));
+  for (int l = 0; l < D.L; ++l) {
+    const auto& o = C.Lo.lay[l];
+    CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, o.ln1w), P(C, o.ln1b), W.h, d, W.mean, W.rstd, B, d, eps, C.s));
+    cg_gemm_desc g = lin_fwd(C, W.h, d, o.wqkv, d, D.Nqkv, d, W.qkv, D.Nqkv);
+    g.epilogue = CG_EPI_BIAS; g.bias = P(C, o.bqkv);
+    CK(cg_gemm(&g, C.s));
+    if (D.rope) CK(cg_rope_pos(C.dt, W.qkv, D.Nqkv, pos, B, D.H, D.KV, D.hd, m->rope_cos, m->rope_sin, Tmax, C.s));
+    char* cl = (char*)cache + (size_t)l * B * Tmax * row;
+    CK(cg_kv_append(C.dt, (const char*)W.qkv + (size_t)d * es, D.Nqkv, cl, 2 * D.kvd, Tmax, pos, B, 2 * D.kvd, C.s));
+    CK(cg_attn_decode_ragged(C.dt, W.qkv, D.Nqkv, cl, 2 * D.kvd, Tmax, pos, m->cfg.sep_id >= 0 ? segstate : nullptr,
+                             m->window, B, D.H, D.KV, D.hd, W.y, d, C.s));
+    g = lin_fwd(C, W.y, d, o.wp, d, d, d, W.xmid, d);
+    g.c_dtype = CG_F32;
+    g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.bp); g.resid = W.x; g.ldr = d;
+    CK(cg_gemm(&g, C.s));
+    CK(cg_layernorm_fwd(C.dt, W.xmid, d, P(C, o.ln2w), P(C, o.ln2b), W.h, d, W.mean, W.rstd, B, d, eps, C.s));
+    if (!D.swiglu) {
+      g = lin_fwd(C, W.h, d, o.w1, d, D.hid, d, W.g, D.hid);
+      g.epilogue = CG_EPI_BIAS | CG_EPI_GELU | CG_EPI_GELU_DERIV; g.bias = P(C, o.b1); g.aux_out = W.a; g.ld_aux = D.hid;
+      CK(cg_gemm(&g, C.s));
+      g = lin_fwd(C, W.g, D.hid, o.w2, D.hid, d, D.hid, W.x, d);
+      g.c_dtype = CG_F32;
+      g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.b2); g.resid = W.xmid; g.ldr = d;
+      CK(cg_gemm(&g, C.s));
+    } else {
+      g = lin_fwd(C, W.h, d, o.wgu, d, 2 * D.Hp, d, W.gu, 2 * D.Hp);
+      CK(cg_gemm(&g, C.s));
+      CK(cg_swiglu_fwd(C.dt, W.gu, 2 * D.Hp, D.Hp, W.s, D.Hp, B, D.hid, C.s));
+      g = lin_fwd(C, W.s, D.Hp, o.wd, D.Hp, d, D.Hp, W.x, d);
+      g.c_dtype = CG_F32;
+      g.epilogue = CG_EPI_RESID; g.resid = W.xmid; g.ldr = d;
+      CK(cg_gemm(&g, C.s));
+    }
+  }
+  CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, C.Lo.lnfw), P(C, C.Lo.lnfb), W.xf, d, W.mean, W.rstd, B, d, eps, C.s));
+  const long long hoff = m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head;
+  cg_gemm_desc g = lin_fwd(C, W.xf, d, hoff, d, D.V, d, lg, D.V);
+  g.c_dtype = CG_F32;
+  CK(cg_gemm(&g, C.s));
+  CK(cg_gather_rows(lg, D.V, pos, 0, Tmax, logits, D.V, D.V, nullptr, nullptr, B, C.s));
+  if (term_logits)
+    CK(cg_row_head(C.dt, W.xf, d, P(C, C.Lo.termw), P(C, C.Lo.termb), pos, Tmax, B, d, nc, term_logits, ld_term, C.s));
+  return CG_OK;
+}
+
 extern "C" size_t cg_struct_bytes(const char* name) {
   if (!name) return 0;
   const std::string n(name);
@@ -1475,9 +1581,9 @@ extern "C" size_t cg_struct_bytes(const char* name) {
   if (n == #T) return sizeof(T);
   CG_SZ(cg_gemm_desc) CG_SZ(cg_dw_product) CG_SZ(cg_dw_group) CG_SZ(cg_reduce_job) CG_SZ(cg_reduce_batch)
   CG_SZ(cg_transpose_item) CG_SZ(cg_transpose_batch) CG_SZ(cg_adamw_segment) CG_SZ(cg_model_cfg)
-  CG_SZ(cg_param_entry) CG_SZ(cg_model) CG_SZ(cg_model_opts)
+  CG_SZ(cg_param_entry) CG_SZ(cg_model) CG_SZ(cg_model_opts) CG_SZ(cg_sample_params) CG_SZ(cg_gen_state)
 #undef CG_SZ
   return 0;
 }
 
-extern "C" const char* cg_version(void) { return "codonlm_hip 0.5 gfx950"; }
+extern "C" const char* cg_version(void) { return "codonlm_hip 0.6 gfx950"; }

@@ -537,6 +537,110 @@ int cg_attn_decode(int dtype, const void* q, long long ldq, const void* cache, l
 /* segstate[b] = pos where tok[b] == sep_id (the SEP token opens its segment) */
 int cg_segstate_step(const int64_t* tok, int B, int sep_id, int pos, int32_t* segstate, void* stream);
 
+/* Ragged decoding (ABI 0.6): every sequence of the batch at its own position, read from a device
+ * int32 pos[B].  A row with pos[b] < 0 or pos[b] >= Tmax is INACTIVE: it writes nothing to the
+ * cache and its outputs (logits, term_logits, segstate) are left untouched.  Same cache layout.
+ *   cg_model_prefill_ragged: eval forward of the right-padded prompts idx [B][T] (pad with any
+ *     token but sep_id; the causal mask keeps rows < len[b] independent of the padding), len[b]
+ *     in 1..T on the device.  Fills cache rows 0..len[b]-1 (one launch per layer), segstate[b]
+ *     as of row len[b]-1 and last_logits [B][V] from row len[b]-1.  The aux heads of the same
+ *     forward are available from cg_model_aux_forward afterwards.
+ *   cg_model_decode_ragged: token tok[b] enters at row pos[b]: the layer sequence of
+ *     cg_model_decode with the per-row ops below.  term_logits (fp32 [B][ld_term], optional,
+ *     needs cfg.termination_aux) receives the termination head of the new row.
+ *     dec_ws: cg_decode_ragged_workspace_bytes(cfg, B). */
+size_t cg_decode_ragged_workspace_bytes(const cg_model_cfg* cfg, int B);
+int cg_model_prefill_ragged(cg_model* m, const int64_t* idx, const int32_t* len, int B, int T, int window,
+                            void* cache, int Tmax, int32_t* segstate, float* last_logits, void* stream);
+int cg_model_decode_ragged(cg_model* m, const int64_t* tok, const int32_t* pos, int B, void* cache, int Tmax,
+                           int32_t* segstate, void* dec_ws, size_t dec_ws_bytes, float* logits,
+                           float* term_logits, long long ld_term, void* stream);
+/* The decode step's attention, one workgroup per (kv head, sequence) serving all H/KV query heads
+ * of the group from each K / V row; rows are read 16 bytes per lane, each wave runs an online
+ * softmax over its share of the keys max(segstate[b], pos[b]-window+1) .. pos[b] and the waves
+ * merge through LDS (no score buffer, any Tmax).  Same operand layout as cg_attn_decode.
+ * fp32 and bf16, hd <= 64, hd a multiple of 8 (bf16) / 4 (fp32), q and cache rows 16-byte
+ * aligned; anything else CG_EUNSUPPORTED. */
+int cg_attn_decode_ragged(int dtype, const void* q, long long ldq, const void* cache, long long ldc, int Tmax,
+                          const int32_t* pos, const int32_t* segstate, int window, int B, int H, int KV, int hd,
+                          void* y, long long ldy, void* stream);
+/* x[b] = tok_emb[tok[b]] (+ pos_emb[pos[b]]), fp32 [B][d] */
+int cg_embed_fwd_pos(const int64_t* tok, const float* tok_emb, const float* pos_emb, const int32_t* pos, float* x,
+                     int B, int d, int V, int Tmax, void* stream);
+/* rotate-half RoPE of the q and k heads of row b of qkv [B][ldqkv] with table row pos[b] */
+int cg_rope_pos(int dtype, void* qkv, long long ldqkv, const int32_t* pos, int B, int H, int KV, int hd,
+                const float* cos_tab, const float* sin_tab, int Tmax, void* stream);
+/* cache[b][pos[b]][0..n) = src[b][0..n): one layer's cache [B][Tmax][ldc], src rows lds apart */
+int cg_kv_append(int dtype, const void* src, long long lds, void* cache, long long ldc, int Tmax,
+                 const int32_t* pos, int B, int n, void* stream);
+/* cache[b][t][0..n) = src[b*T + t][0..n) for t < len[b]: a prefill's cache fill of one layer */
+int cg_kv_scatter(int dtype, const void* src, long long lds, int T, void* cache, long long ldc, int Tmax,
+                  const int32_t* len, int B, int n, void* stream);
+/* segstate[b] = pos[b] where tok[b] == sep_id */
+int cg_segstate_step_ragged(const int64_t* tok, const int32_t* pos, int B, int sep_id, int Tmax, int32_t* segstate,
+                            void* stream);
+/* dst[b][0..n) = src[row][0..n), fp32.  T > 0: row = b*T + sel[b]-1 (sel = prompt lengths), and
+ * seg_dst[b] = seg_src[row] (0 without seg_src) when seg_dst is given.  T == 0: row = b, only
+ * where sel[b] is an active position. */
+int cg_gather_rows(const float* src, long long lds, const int32_t* sel, int T, int Tmax, float* dst, long long ldd,
+                   int n, const int32_t* seg_src, int32_t* seg_dst, int B, void* stream);
+/* out[b][c] = xf[b] . w[c] + bias[c] (w fp32 [nc][d]) on the active rows */
+int cg_row_head(int dtype, const void* xf, long long ldx, const float* w, const float* bias, const int32_t* pos,
+                int Tmax, int B, int d, int nc, float* out, long long ldo, void* stream);
+
+/* The fused sampler and stop-rule step of batched generation (ABI 0.6; the rules of the
+ * reference's generate.py :51-59, :111-127, :193-260): one launch per generated token, one
+ * workgroup per sequence, V <= 1024 (else CG_EUNSUPPORTED).  tok_class[v] is a bit set of
+ * CG_TOK_*; a stop codon is CG_TOK_CODON | CG_TOK_STOP.  For each sequence not yet CG_GEN_DONE:
+ *  1. termination bias, only with term_logits, stop_bias > 0 and
+ *     n_codons >= max(0, target_codons - bias_window): cls = argmax(term_logits[b][:n_term_classes])
+ *     (lowest index on ties), last_term_class = cls; if cls <= trigger_class_max every
+ *     CG_TOK_STOP token's logit gains stop_bias and bias_steps grows by one;
+ *  2. tokens with allowed[v] == 0 get weight 0 (at least one token must stay allowed);
+ *  3. w_v = exp((l_v - max) / max(1e-6, temperature)), max over the allowed tokens;
+ *  4. topk > 0: the min(topk, V) largest weights are kept, ties to the lower token index;
+ *  5. the draw: u = (h >> 8) * 2^-24 with
+ *         h = fmix32(row_hash(seed, state.stream) + n_tokens * 0x9E3779B1u),
+ *     fmix32 the murmur3 finaliser and row_hash(s, r) = fmix32(s ^ (r * 0x9E3779B1u)) (csrc/common.h
+ *     cg_fmix32 / cg_row_hash), all in uint32 arithmetic.  The token is the first index, in
+ *     ascending token order, whose inclusive cumulative weight exceeds u * total, else the last
+ *     kept index with a positive weight.  Steps 1-5 are evaluated in fp64 from the fp32 logits.
+ *     A sequence's draws depend on (seed, stream, n_tokens) only, not on its place in a batch;
+ *  6. next_tok[b] = out_ids[b][n_tokens] = token; n_tokens++; n_codons++ for a CG_TOK_CODON token;
+ *  7. stop rules, the first that fires ends the sequence:
+ *     CG_TOK_STOP with stop_on_bio_stop: n_codons < target_codons sets EARLY_STOP and, unless
+ *       require_terminal_stop, TERMINAL_STOP|DONE; n_codons >= target_codons sets TERMINAL_STOP|DONE;
+ *     CG_TOK_EOS with stop_on_eos: EOS|DONE if n_codons >= target_codons or !require_terminal_stop;
+ *     n_codons >= target_codons and !require_terminal_stop: TARGET|DONE;
+ *     n_codons >= max_codons or n_tokens >= max_tokens: CAP|DONE;
+ *  8. not DONE: pos = pos0 + n_tokens - 1, the cache row the next cg_model_decode_ragged writes this
+ *     token to (pos0 = the prompt length); pos >= Tmax sets CONTEXT_FULL|DONE.  DONE: pos = -1;
+ *  9. n_active (optional, device) = number of sequences still running after the step.
+ * A DONE sequence's state, next_tok and out_ids are not touched. */
+enum { CG_TOK_CODON = 1, CG_TOK_STOP = 2, CG_TOK_EOS = 4 };
+enum { CG_GEN_DONE = 1, CG_GEN_TERMINAL_STOP = 2, CG_GEN_EARLY_STOP = 4, CG_GEN_EOS = 8,
+       CG_GEN_TARGET = 16, CG_GEN_CAP = 32, CG_GEN_CONTEXT_FULL = 64 };
+typedef struct {
+  int V;
+  const uint8_t* tok_class; /* device [V] */
+  const uint8_t* allowed;   /* device [V] or NULL = every token */
+  float temperature;
+  int topk;
+  int target_codons, max_codons, max_tokens; /* INT_MAX = off */
+  int require_terminal_stop, stop_on_eos, stop_on_bio_stop;
+  float stop_bias;
+  int trigger_class_max, bias_window, n_term_classes;
+  uint32_t seed;
+  int Tmax;
+} cg_sample_params;
+typedef struct {
+  int32_t pos0, pos, n_tokens, n_codons, flags, bias_steps, last_term_class; /* last_term_class -1 = none */
+  uint32_t stream;
+} cg_gen_state;
+int cg_sample_step(const cg_sample_params* p, const float* logits, long long ldl, const float* term_logits,
+                   long long ld_term, cg_gen_state* state, int64_t* next_tok, int64_t* out_ids, long long ld_out,
+                   int32_t* n_active, int B, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -572,7 +676,8 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
 
 /* sizeof the named ABI struct ("cg_gemm_desc", "cg_dw_product", "cg_dw_group", "cg_reduce_job",
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
- * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts"), 0 for another name: lets a binding that mirrors
+ * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state"), 0 for
+ * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
 
@@ -583,7 +688,10 @@ size_t cg_struct_bytes(const char* name);
  * cg_gemm_set_* calls and the environment switches; cg_model_dw_plan takes (B, T) and reports the
  * token split; cg_model.embed_done is gone.  ABI 0.5 (round 6): the fused attention backward --
  * cg_attn_bwd_algo, cg_model_opts.attn_bwd_algo, CG_PROBE_ATTN_BWD; cg_attn_bwd_workspace also
- * covers the fused pass's dQ accumulator. */
+ * covers the fused pass's dQ accumulator.  ABI 0.6: batched on-device generation, additions only --
+ * the ragged decode entry points (cg_model_prefill_ragged, cg_model_decode_ragged,
+ * cg_decode_ragged_workspace_bytes and their per-row ops, cg_attn_decode_ragged among them) and
+ * cg_sample_step with cg_sample_params / cg_gen_state. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

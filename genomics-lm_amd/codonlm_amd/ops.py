@@ -547,18 +547,20 @@ def transpose16(mats):
     return outs
 
 
-def gemm_dw_grouped(products, *, tile_m=0, ksplit=1):
+def gemm_dw_grouped(products, *, tile_m=0, ksplit=1, max_wg=0, workspace=None):
     """Grouped weight gradients: for each (dy [K, N_out] bf16, x [K, K_out] bf16, out fp32
     [N_out, K_out], alpha, accumulate[, col_sum]) -> out (+)= alpha * dy^T x, one persistent launch
     (cg_gemm_dw_grouped).  Row strides are taken from the tensors.  ksplit > 1: each tile's K rows
     split over that many workgroups (fp32 slabs + one in-order reduction).  col_sum (fp32 [N_out],
-    optional): (+)= alpha * the column sums of dy (the bias gradient), ksplit 1 only."""
+    optional): (+)= alpha * the column sums of dy (the bias gradient), ksplit 1 only.  max_wg > 0
+    caps the persistent grid (0: one workgroup per CU); workspace (fp32, ksplit > 1): the caller's
+    slab buffer instead of a fresh one."""
     if not products:
         return
     if len(products) > L.DW_MAX:
         raise ValueError(f"at most {L.DW_MAX} products per group")
     g = L.DwGroup()
-    g.n, g.tile_m = len(products), int(tile_m)
+    g.n, g.tile_m, g.max_wg = len(products), int(tile_m), int(max_wg)
     K = None
     for i, (dy, x, out, alpha, acc, *cs) in enumerate(products):
         for t in (dy, x, out):
@@ -586,7 +588,13 @@ def gemm_dw_grouped(products, *, tile_m=0, ksplit=1):
     if ksplit > 1:
         g.ksplit = int(ksplit)
         nbytes = int(L.lib.cg_gemm_dw_grouped_workspace(C.byref(g)))
-        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=products[0][0].device)
+        ws = workspace
+        if ws is None:
+            ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=products[0][0].device)
+        elif ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() * 4 < nbytes:
+            raise ValueError(f"gemm_dw_grouped: workspace must be contiguous fp32 of at least {nbytes} bytes")
+        else:
+            L.require_device(ws, "gemm_dw_grouped")
         g.workspace, g.ws_bytes = ws.data_ptr(), ws.numel() * 4
     L.check(L.lib.cg_gemm_dw_grouped(C.byref(g), L.stream_ptr(products[0][0].device)), "cg_gemm_dw_grouped")
     return ws

@@ -69,7 +69,7 @@ bool dims_of(const cg_model_cfg* c, Dims& D) {
 // persistent launch with one workgroup per CU and every tile costing about the same (full-token
 // reduction), so a group takes ceil(tiles / CUs) rounds of its tile's cost.  Tile candidates
 // (cg_gemm_dw_tiles codes): 128 x 128 (cost 1), 256 x 128 (1.38: twice the work in 1.38x the
-// time) and 256 x 256 (2.35: 4x the work; a 2-stage ring, its DMA latency partly exposed),
+// time) and 256 x 256 (2.35: 4x the work; measured on its first, 2-stage ring -- see dw_tile_for),
 // measured at K = 16384 on the C4/C5 shapes (tools/dw_grouped.py).  Each group takes its
 // cheapest tile (a short remainder group often prefers the smaller tile); the plan minimises the
 // summed cost of the groups (G, G, ..., remainder) and, on ties, prefers the smaller group (its
@@ -96,7 +96,13 @@ static int dw_tile_for(const Dims& D, int n, double* cost_out, int* ks_out, long
   for (int bm : {128, 256, 512}) {
     // (256 x 256: 2.35 at K = 16384 on C4/C5; 2.49 at C3, K = 32768: 951 vs 526 us per round of
     // the 256 x 128 tile, rocprofv3 -- 2.5 keeps C4 on its 5/5/2 plan and moves C3 from 6/4 to
-    // 4/4/2, 9.08 -> 8.99 ms/step, profiles/round4/dw_sweep)
+    // 4/4/2, 9.08 -> 8.99 ms/step, profiles/round4/dw_sweep).  On the ring of 32-token stages an
+    // unsplit round of the tile measures 2.28 (C4, K = 32768: 816.6 us against 2 x 494.9 us of the
+    // 256 x 128 tile, profiles/dw_ring/dw_grouped_tile_costs.txt).  Priced at 2.27, C2, C4 and C5
+    // keep their plans and C3 moves from 6/4 of the 256 x 128 tile to 5/5 of this one, both split
+    // 3 ways -- which measured 0.1 - 0.9 ms/step slower in each of 3 interleaved rounds
+    // (profiles/dw_ring/dw_cost_227_ab.txt): the tile split over the tokens does not reach its
+    // unsplit rate, so the price stays at the value that keeps C3's plan.
     const double tile_cost = bm == 128 ? 1.0 : bm == 256 ? 1.38 : 2.5;
     const int per_layer = cg_gemm_dw_tiles(bm, D.Nqkv, d) + cg_gemm_dw_tiles(bm, d, d) +
                           (D.swiglu ? cg_gemm_dw_tiles(bm, 2 * D.Hp, d) + cg_gemm_dw_tiles(bm, d, D.Hp)

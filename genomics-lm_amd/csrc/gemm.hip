@@ -935,19 +935,22 @@ extern "C" int cg_gemm(const cg_gemm_desc* d, void* stream) {
 // ---------------------------------------------------------------------------
 // grouped weight-gradient GEMM (gemm_dw.h)
 // ---------------------------------------------------------------------------
+#ifndef DW_RING_SLOTS  // (4 for the A/B build of the 128 KB ring, tools/build_variant.sh)
+#define DW_RING_SLOTS 5
+#endif
 static bool dw_tile_code(int bm) { return bm == 128 || bm == 129 || bm == 256 || bm == 512; }
 // tile codes: 128 / 129 = 128 x 128 (4 / 5 ring stages), 256 = 256 x 128 (3 stages),
-// 512 = 256 x 256 (2 stages of 64 KiB)
+// 512 = 256 x 256 (5 stages of 32 tokens, 32 KiB each; fragments read one stage ahead)
 extern "C" int cg_gemm_dw_tiles(int bm, int N_out, int K_out) {
   if (!dw_tile_code(bm)) bm = 128;
   return cg_cdiv(N_out, bm >= 256 ? 256 : 128) * cg_cdiv(K_out, bm == 512 ? 256 : 128);
 }
-template <int BM, int NS, int BNT = bfd::BN>
+template <int BM, int NS, int BNT = bfd::BN, int BKT = DW_KUNIT>
 static int launch_dw(bfd::Params& P, hipStream_t s) {
-  using G = bfd::Geo<BM, NS, BNT>;
+  using G = bfd::Geo<BM, NS, BNT, BKT>;
   bool cs = false;
   for (int i = 0; i < P.nprod; ++i) cs |= P.p[i].colsum != nullptr;
-  auto kern = cs ? gemm_dw_kernel<BM, NS, BNT, true> : gemm_dw_kernel<BM, NS, BNT, false>;
+  auto kern = cs ? gemm_dw_kernel<BM, NS, BNT, true, BKT> : gemm_dw_kernel<BM, NS, BNT, false, BKT>;
   int ntiles = 0;
   for (int i = 0; i < P.nprod; ++i) {
     bfd::Prod& pr = P.p[i];
@@ -957,7 +960,7 @@ static int launch_dw(bfd::Params& P, hipStream_t s) {
   }
   P.ntiles = ntiles * P.ksplit;
   if (!ntiles) return CG_OK;
-  if (P.ksplit > 1) P.kc_steps = cg_cdiv(cg_cdiv(P.K, P.ksplit), bfd::BKT);
+  if (P.ksplit > 1) P.kc_steps = dw_kc_steps(P.K, P.ksplit);
   const int grid = std::min(P.ntiles, P.max_wg > 0 ? P.max_wg : cg_pers_cus());
   cg_func_lds((const void*)kern, G::SMEM);
   double flops = 0, bytes = 0;
@@ -1038,9 +1041,9 @@ extern "C" int cg_gemm_dw_grouped(const cg_dw_group* grp, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int bm = grp->tile_m > 0 ? grp->tile_m : 128;
   P.max_wg = grp->max_wg;
-  // tile_m codes: 128 / 256 = rows of the C tile (ring of 4 / 3 stages); 129 / 257 = the same
-  // tile with one more ring stage (5 / 4... 160 KB LDS for 128)
-  if (bm == 512) return launch_dw<256, 2, 256>(P, s);
+  // tile_m codes: 128 / 256 = rows of the C tile (ring of 4 / 3 stages); 129 = the 128-row tile
+  // with one more ring stage (160 KB LDS); 512 = 256 x 256 on five 32-token stages (160 KB)
+  if (bm == 512) return launch_dw<256, DW_RING_SLOTS, 256, 32>(P, s);
   if (bm == 256) return launch_dw<256, 3>(P, s);
   if (bm == 129) return launch_dw<128, 5>(P, s);
   return launch_dw<128, 4>(P, s);

@@ -103,7 +103,8 @@ int cg_pers_cus(void);
  * (dW = dY^T X of the nn.Linear call sites, A = dY and B = X both token-major bf16, C fp32).
  * Each output tile is reduced over all K rows inside one workgroup (no split-K partials);
  * the tiles of all products form one persistent launch (tile_m codes: 128 = 128x128 (0 = this),
- * 129 = the same with a 5-stage ring, 256 = 256x128, 512 = 256x256).  Any K >= 1 (a ragged last 64-row k-step is zero-filled);
+ * 129 = the same with a 5-stage ring, 256 = 256x128, 512 = 256x256 on a ring of five 32-token
+ * stages).  Any K >= 1 (a ragged last 64-row k-step is zero-filled);
  * N_out, K_out, lda, ldb % 8 == 0; ldc % 4. */
 #define CG_DW_MAX 32
 typedef struct {

@@ -1,5 +1,7 @@
 """Grouped dW GEMM (cg_gemm_dw_grouped) vs the split-K dW path on the C4/C5 block products:
-correctness against torch fp32 of the same bf16 operands, then device time per layer."""
+correctness against torch fp32 of the same bf16 operands, then device time per layer.
+
+    python tools/dw_grouped.py [M ...]"""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "genomics-lm_amd"))
@@ -33,7 +35,10 @@ def timeit(fn, reps=10):
     return e0.elapsed_time(e1) / reps * 1e3  # us
 
 
-for name, (M, d, nqkv, hid) in {"c4": (16384, 512, 1536, 2048), "c5": (16384, 384, 1152, 1536)}.items():
+# token counts M from the command line (default 16384; the C4 / C3 bench steps run 32768)
+Ms = [int(v) for v in sys.argv[1:]] or [16384]
+for name, (M, d, nqkv, hid) in {f"{c} M={M}": (M, *dims) for M in Ms
+                                for c, dims in {"c4": (512, 1536, 2048), "c5": (384, 1152, 1536)}.items()}.items():
     prods = layer_products(M, d, nqkv, hid)
     # correctness (one product of each shape, both tiles)
     for bm in (128, 256, 512):

@@ -157,6 +157,14 @@ class GenState(C.Structure):
 GEN_STATE_FIELDS = tuple(f for f, _ in GenState._fields_)  # the int32 columns of a (B, 8) state tensor
 
 
+class ScoreDesc(C.Structure):
+    """cg_score_desc: every output pointer optional (None = not wanted)"""
+    _fields_ = [("logits", vp), ("ldl", i64), ("rows", i32), ("V", i32), ("targets", vp), ("ignore_index", i32),
+                ("smoothing", f32), ("lse", vp), ("logp", vp), ("entropy", vp), ("argmax", vp), ("rank", vp),
+                ("sel", vp), ("n_sel", i32), ("delta", vp), ("ld_delta", i64), ("T", i32),
+                ("seq_logp", vp), ("seq_count", vp), ("acc", vp), ("workspace", vp), ("ws_bytes", sz)]
+
+
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {
     "cg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -237,6 +245,8 @@ SIGNATURES = {
     "cg_gather_rows": (i32, [vp, i64, vp, i32, i32, vp, i64, i32, vp, vp, i32, vp]),
     "cg_row_head": (i32, [i32, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
     "cg_sample_step": (i32, [C.POINTER(SampleParams), vp, i64, vp, i64, vp, vp, vp, i64, vp, i32, vp]),
+    "cg_score_workspace": (sz, [i32]),
+    "cg_score_rows": (i32, [C.POINTER(ScoreDesc), vp]),
     "cg_model_hidden": (vp, [C.POINTER(Model), i32, C.POINTER(i32), C.POINTER(i64)]),
     "cg_model_attn_probs": (i32, [C.POINTER(Model), i32, vp, vp]),
     "cg_probe_enable": (i32, [i32]),

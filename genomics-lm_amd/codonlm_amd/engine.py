@@ -193,6 +193,25 @@ class Engine:
                 "cg_model_forward")
         return logits, loss
 
+    @torch.no_grad()
+    def score(self, idx: torch.Tensor, targets: torch.Tensor | None = None, *, window: int | None = None, **kw):
+        """Eval forward of idx (B, T) without a loss, then cg_score_rows over the engine's own
+        logits buffer, in place: an ops.ScoreResult whose rows are the B*T positions (``T`` rows
+        per sequence).  ``kw``: the keywords of ops.score_rows (ignore_index, smoothing, sel, acc,
+        want).  The logits stay in ``score_logits`` (B, T, V) until the next score call."""
+        from . import ops
+        B, T = idx.shape
+        V = self.cfg.vocab_size
+        buf = getattr(self, "_score_buf", None)
+        if buf is None or buf.numel() < B * T * V or buf.device != self.flat.device:
+            buf = self._score_buf = torch.empty(B * T * V, dtype=torch.float32, device=self.flat.device)
+        self.score_logits = buf[:B * T * V].view(B, T, V)
+        self.forward(idx, None, training=False, window=window, logits=self.score_logits)
+        wsb = getattr(self, "_score_ws", None)
+        if wsb is None or wsb.numel() * 8 < int(L.lib.cg_score_workspace(B * T)) or wsb.device != buf.device:
+            wsb = self._score_ws = ops.score_workspace(B * T, buf.device)
+        return ops.score_rows(self.score_logits.view(B * T, V), targets, T=T, workspace=wsb, **kw)
+
     def aux_forward(self):
         """Aux heads of the last forward (model_tiny_gpt.py:329-337): termination logits
         fp32 (M, n_classes) or None, and [offset logits fp32 (M, V)] in offset order."""

@@ -441,6 +441,95 @@ def sample_step(params, logits, state, next_tok, out_ids, n_active=None, term_lo
                                  L.stream_ptr(logits.device)), "cg_sample_step")
 
 
+def gather_rows(src, sel, T):
+    """cg_gather_rows with T > 0: out[b] = src[b*T + sel[b] - 1] for fp32 src [B*T][n] and a device
+    int32 sel [B] of 1-based row counts (sel = T picks every sequence's last row)."""
+    L.require_device(src, "gather_rows")
+    if src.dim() != 2 or src.dtype != torch.float32 or src.stride(1) != 1 or T <= 0 or src.shape[0] % T:
+        raise ValueError("gather_rows: src is fp32 [B*T][n]")
+    B, n = src.shape[0] // T, src.shape[1]
+    if sel.dtype != torch.int32 or sel.numel() != B or not sel.is_cuda or not sel.is_contiguous():
+        raise ValueError("gather_rows: sel is a contiguous device int32 [B]")
+    out = torch.empty(B, n, dtype=torch.float32, device=src.device)
+    L.check(L.lib.cg_gather_rows(src.data_ptr(), src.stride(0), sel.data_ptr(), int(T), int(T), out.data_ptr(), n, n,
+                                 None, None, B, L.stream_ptr(src.device)), "cg_gather_rows")
+    return out
+
+
+class ScoreResult:
+    """Device tensors of one score_rows call; an output that was not asked for is None."""
+    __slots__ = ("lse", "logp", "entropy", "argmax", "rank", "delta", "seq_logp", "seq_count", "acc")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
+SCORE_OUTPUTS = ("lse", "logp", "entropy", "argmax", "rank", "delta", "seq_logp", "seq_count")
+
+
+def score_workspace(rows, device):
+    """A cg_score_rows workspace for up to ``rows`` rows (8-byte aligned)."""
+    return torch.empty(int(L.lib.cg_score_workspace(int(rows))) // 8 + 1, dtype=torch.float64, device=device)
+
+
+def score_rows(logits, targets=None, *, V=None, ignore_index=0, smoothing=0.0, sel=None, T=0, acc=None,
+               want=("lse", "logp", "entropy", "argmax", "rank"), workspace=None):
+    """cg_score_rows over fp32 logits [rows][ld] (only the first ``V`` columns of a row are read):
+    a ScoreResult with the row outputs named in ``want`` (fp32 lse / logp / entropy, int32 argmax /
+    rank), ``delta`` fp32 [rows][len(sel)] for the device int32 class list ``sel``, ``seq_logp``
+    fp64 [rows / T] and ``seq_count`` int32 with ``T`` rows per sequence, and ``acc``: the fp64 [4]
+    accumulator the launch added to (nll sum, smoothed sum, valid rows, top-1 hits)."""
+    L.require_device(logits, "score_rows")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[0] and logits.stride(1) != 1):
+        raise ValueError("score_rows: logits is fp32 [rows][ld] with contiguous rows")
+    unknown = set(want) - set(SCORE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"score_rows: unknown outputs {sorted(unknown)}")
+    rows = logits.shape[0]
+    V = logits.shape[1] if V is None else int(V)
+    dev = logits.device
+    d = L.ScoreDesc()
+    d.logits, d.ldl, d.rows, d.V = logits.data_ptr(), logits.stride(0) if rows else V, rows, V
+    if targets is not None:
+        L.require_device(targets, "score_rows")
+        targets = targets.reshape(-1).to(torch.int64).contiguous()
+        if targets.numel() != rows:
+            raise ValueError("score_rows: one target per row")
+        d.targets = targets.data_ptr()
+    d.ignore_index, d.smoothing, d.T = int(ignore_index), float(smoothing), int(T)
+    res = ScoreResult()
+    for name, dt in (("lse", torch.float32), ("logp", torch.float32), ("entropy", torch.float32),
+                     ("argmax", torch.int32), ("rank", torch.int32)):
+        if name in want:
+            t = torch.empty(rows, dtype=dt, device=dev)
+            setattr(res, name, t)
+            setattr(d, name, t.data_ptr())
+    if "delta" in want or sel is not None:
+        if sel is None or sel.dtype != torch.int32 or not sel.is_cuda or not sel.is_contiguous() or sel.numel() < 1:
+            raise ValueError("score_rows: delta needs sel, a contiguous device int32 class list")
+        res.delta = torch.empty(rows, sel.numel(), dtype=torch.float32, device=dev)
+        d.sel, d.n_sel, d.delta, d.ld_delta = sel.data_ptr(), sel.numel(), res.delta.data_ptr(), sel.numel()
+    if "seq_logp" in want or "seq_count" in want:
+        if T <= 0 or rows % T:
+            raise ValueError("score_rows: sequence sums need T > 0 dividing the row count")
+        if "seq_logp" in want:
+            res.seq_logp = torch.empty(rows // T, dtype=torch.float64, device=dev)
+            d.seq_logp = res.seq_logp.data_ptr()
+        if "seq_count" in want:
+            res.seq_count = torch.empty(rows // T, dtype=torch.int32, device=dev)
+            d.seq_count = res.seq_count.data_ptr()
+    if acc is not None:
+        if acc.dtype != torch.float64 or acc.numel() != 4 or not acc.is_cuda or not acc.is_contiguous():
+            raise ValueError("score_rows: acc is a contiguous device fp64 [4]")
+        res.acc = acc
+        d.acc = acc.data_ptr()
+    ws = workspace if workspace is not None else score_workspace(rows, dev)
+    d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    L.check(L.lib.cg_score_rows(C.byref(d), L.stream_ptr(dev)), "cg_score_rows")
+    return res
+
+
 def attn_probs(qkv, segstart, lse, B, T, H, KV, hd, window=0):
     """softmax(QK^T / sqrt(hd)) on the visible (query, key) pairs from the forward's qkv rows and
     LSE, 0 elsewhere: fp32 [B][H][T][T]."""

@@ -642,6 +642,52 @@ int cg_sample_step(const cg_sample_params* p, const float* logits, long long ldl
                    long long ld_term, cg_gen_state* state, int64_t* next_tok, int64_t* out_ids, long long ld_out,
                    int32_t* n_active, int B, void* stream);
 
+/* Batched scoring (ABI 0.6 addition): one fused pass over fp32 logits rows [rows][ldl], of which
+ * only the first V columns are read (V <= 1024, else CG_EUNSUPPORTED).  It replaces the
+ * log_softmax / gather / F.cross_entropy passes of the reference's scoring scripts
+ * (score_mutations.py :95-157, evaluate_test.py :86-171, benchmark_zero_shot_mutations.py :25-41).
+ * All row arithmetic is fp64 from the fp32 logits; every fp32 output is the single rounding of
+ * the fp64 value.  Every output pointer is optional (NULL = not wanted).
+ *   Row r with logits z: y = targets[r] (when targets is given); the row is VALID when targets !=
+ *   NULL, y != ignore_index and 0 <= y < V.
+ *     lse[r]     = log sum_c exp z_c
+ *     logp[r]    = z_y - lse on a valid row, else 0
+ *     entropy[r] = lse - sum_c p_c z_c (columns with p_c == 0, i.e. z_c = -inf, add 0)
+ *     argmax[r]  = the lowest index among the maxima
+ *     rank[r]    = #{c : z_c > z_y} + #{c < y : z_c == z_y} on a valid row (0 = top-1), else -1
+ *   Selected classes (the mutation map): sel = device int32 [n_sel], delta fp32 [rows][ld_delta]:
+ *     delta[r][j] = (z_sel[j] - lse) - base_r, base_r = the row's fp64 logp (0 on an invalid row);
+ *     -inf where sel[j] < 0 or sel[j] >= V.
+ *   Per-sequence sums, T > 0 and rows = B * T: seq_logp[b] (fp64) = sum of logp over the valid rows
+ *     of sequence b, seq_count[b] = their number.  Lane t % 64 of one wave adds row t of the
+ *     sequence in order and a fixed butterfly follows; invalid rows add exactly 0: a sequence's
+ *     sum is bitwise independent of its padding and of the rest of the batch.
+ *   acc (device fp64 [4], += across launches): [0] sum of nll = -logp over the valid rows,
+ *     [1] sum of (1 - smoothing) nll + (smoothing / V) sum_c (lse - z_c) (F.cross_entropy with
+ *     label_smoothing, ignore_index, reduction="sum", no class weights), [2] the number of valid
+ *     rows, [3] the number of valid rows with argmax == y.  Per-workgroup fp64 partials go to the
+ *     workspace and one single-workgroup launch adds them in a fixed order (no floating-point
+ *     atomics): the same inputs give the same bits.
+ * workspace: 8-byte aligned, ws_bytes >= cg_score_workspace of the row count (else CG_EINVAL).
+ * rows == 0 is CG_OK and touches nothing. */
+typedef struct {
+  const float* logits; long long ldl;
+  int rows, V;
+  const int64_t* targets;  /* device [rows] or NULL */
+  int ignore_index;
+  float smoothing;
+  float* lse; float* logp; float* entropy;
+  int32_t* argmax; int32_t* rank;
+  const int32_t* sel; int n_sel;
+  float* delta; long long ld_delta;
+  int T;
+  double* seq_logp; int32_t* seq_count;
+  double* acc;
+  void* workspace; size_t ws_bytes;
+} cg_score_desc;
+size_t cg_score_workspace(int rows);
+int cg_score_rows(const cg_score_desc* d, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -677,7 +723,8 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
 
 /* sizeof the named ABI struct ("cg_gemm_desc", "cg_dw_product", "cg_dw_group", "cg_reduce_job",
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
- * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state"), 0 for
+ * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
+ * "cg_score_desc"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -692,7 +739,8 @@ size_t cg_struct_bytes(const char* name);
  * covers the fused pass's dQ accumulator.  ABI 0.6: batched on-device generation, additions only --
  * the ragged decode entry points (cg_model_prefill_ragged, cg_model_decode_ragged,
  * cg_decode_ragged_workspace_bytes and their per-row ops, cg_attn_decode_ragged among them) and
- * cg_sample_step with cg_sample_params / cg_gen_state. */
+ * cg_sample_step with cg_sample_params / cg_gen_state.  ABI 0.6, additions: batched scoring --
+ * cg_score_rows with cg_score_desc, and cg_score_workspace. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

@@ -156,6 +156,14 @@ class GenState(C.Structure):
 
 GEN_STATE_FIELDS = tuple(f for f, _ in GenState._fields_)  # the int32 columns of a (B, 8) state tensor
 
+GEN_PLAN_END = 128  # cg_sample_step_plan: the sequence's plan was used up
+
+
+class SamplePlan(C.Structure):
+    """cg_sample_plan: per-step token sets and the drawn tokens' log-probabilities"""
+    _fields_ = [("sets", vp), ("n_sets", i32), ("ld_sets", i64), ("plan", vp), ("ld_plan", i64),
+                ("plan_len", vp), ("end_with_plan", i32), ("logp", vp), ("tok_logp", vp), ("ld_tok_logp", i64)]
+
 
 class ScoreDesc(C.Structure):
     """cg_score_desc: every output pointer optional (None = not wanted)"""
@@ -245,6 +253,8 @@ SIGNATURES = {
     "cg_gather_rows": (i32, [vp, i64, vp, i32, i32, vp, i64, i32, vp, vp, i32, vp]),
     "cg_row_head": (i32, [i32, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
     "cg_sample_step": (i32, [C.POINTER(SampleParams), vp, i64, vp, i64, vp, vp, vp, i64, vp, i32, vp]),
+    "cg_sample_step_plan": (i32, [C.POINTER(SampleParams), C.POINTER(SamplePlan), vp, i64, vp, i64, vp, vp, vp, i64, vp,
+                                  i32, vp]),
     "cg_score_workspace": (sz, [i32]),
     "cg_score_rows": (i32, [C.POINTER(ScoreDesc), vp]),
     "cg_model_hidden": (vp, [C.POINTER(Model), i32, C.POINTER(i32), C.POINTER(i64)]),

@@ -15,7 +15,12 @@ are stated in include/codonlm_hip.h (cg_sample_step).
 ``batch_red_sampler`` take the reference's arguments (plus ``seed`` / ``stream``) and return the
 reference's ``info`` records.  The batched path does not slide the context window: prompt +
 token cap must fit block_size (``query_model.generate`` keeps the sliding loop).  Multi-offset
-priors and the critic-guided / synonymous generators are not part of it.
+priors and the critic-guided generator are not part of it.
+
+``generate_cds_synonymous`` writes a CDS that translates to a given protein: with ``token_sets``
+and ``plans``, ``generate_batch`` goes through cg_sample_step_plan, where every generated token
+of every sequence has its own allowed set, a sequence ends when its plan is used up, and the
+sampler returns the log-probability of what it drew (``with_logp``).
 """
 from __future__ import annotations
 
@@ -29,6 +34,14 @@ from . import _lib as L
 
 STOP_CODONS = {"TAA", "TAG", "TGA"}
 INT_MAX = L.INT_MAX
+
+# the standard genetic code over the codons in ACGT order, stop written as "_"
+_CODE = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV_Y_YSSSS_CWCLFLF"
+CODON_TABLE: Dict[str, str] = {a + b + c: _CODE[16 * i + 4 * j + k] for i, a in enumerate("ACGT")
+                               for j, b in enumerate("ACGT") for k, c in enumerate("ACGT")}
+AA_TO_CODONS: Dict[str, List[str]] = {}
+for _codon, _aa in CODON_TABLE.items():
+    AA_TO_CODONS.setdefault(_aa, []).append(_codon)
 
 
 def _is_codon(tok: str) -> bool:
@@ -78,6 +91,75 @@ def _check_fit(model, contexts, max_tokens: int) -> None:
                          "(query_model.generate does)")
 
 
+def _check_fit_plans(model, contexts, plans) -> None:
+    """The fit check of a batch that ends with its plans: per row, prompt + plan <= block_size."""
+    if not contexts or any(len(c) < 1 for c in contexts):
+        raise ValueError("every context needs at least one token")
+    for b, (c, pl) in enumerate(zip(contexts, plans)):
+        if len(pl) < 1:
+            raise ValueError(f"end_with_plan: sequence {b} has an empty plan and would never end")
+        if len(c) + len(pl) > int(model.block_size):
+            raise ValueError(f"prompt ({len(c)} tokens) + plan ({len(pl)} tokens) of sequence {b} exceeds "
+                             f"block_size {int(model.block_size)}: the batched path does not slide the context "
+                             "window")
+
+
+class TokenSets:
+    """The set table of a planned batch: uint8 rows over the model's V tokens, equal sets stored
+    once.  ``residue`` / ``stop`` / ``token`` return the index of a set, for use in a plan."""
+
+    def __init__(self, stoi: Dict[str, int], itos: Sequence[str], V: int):
+        self.stoi, self.itos, self.V = stoi, itos, int(V)
+        self.rows: List[np.ndarray] = []
+        self._index: Dict[bytes, int] = {}
+
+    def add(self, ids) -> int:
+        row = np.zeros(self.V, dtype=np.uint8)
+        ids = [int(i) for i in ids]
+        if any(i < 0 or i >= self.V for i in ids):
+            raise ValueError(f"token id outside the model's vocabulary of {self.V}")
+        row[ids] = 1
+        key = row.tobytes()
+        if key not in self._index:
+            self._index[key] = len(self.rows)
+            self.rows.append(row)
+        return self._index[key]
+
+    def codon_ids(self, aa: str) -> List[int]:
+        """The ids of the codons of amino acid ``aa`` (any case) that the vocabulary has."""
+        return [self.stoi[c] for c in AA_TO_CODONS.get(aa.upper(), []) if c in self.stoi]
+
+    def residue(self, aa: str, *, strict: bool = False) -> int:
+        """The synonymous set of one residue.  A residue without a codon in the vocabulary (and,
+        when ``strict``, the stop "_") is a ValueError when ``strict``, else the set of all codon
+        tokens (generate.py:673-676)."""
+        ids = self.codon_ids(aa)
+        if not ids or (strict and aa == "_"):
+            if strict:
+                raise ValueError(f"unknown residue {aa!r}: no codon of the vocabulary translates to it")
+            ids = np.nonzero(cds_mask(self.itos))[0]
+        return self.add(ids)
+
+    def stop(self) -> int:
+        return self.add(self.codon_ids("_"))
+
+    def token(self, tok: int) -> int:
+        return self.add([tok])
+
+    def array(self) -> np.ndarray:
+        return np.stack(self.rows) if self.rows else np.zeros((0, self.V), dtype=np.uint8)
+
+
+def synonymous_plan(sets: TokenSets, protein: str, *, strict: bool = False) -> List[int]:
+    """One synonymous set per residue of ``protein``, then the stop-codon set."""
+    return [sets.residue(aa, strict=strict) for aa in protein] + [sets.stop()]
+
+
+def translate(codons: Sequence[str]) -> str:
+    """The protein of a codon list, stop as "_"; "?" for a token that is no codon."""
+    return "".join(CODON_TABLE.get(c, "?") for c in codons)
+
+
 @torch.no_grad()
 def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos: List[str], *, seed: int,
                    streams: Sequence[int] | None = None, poll_every: int = 16, max_tokens: int,
@@ -86,13 +168,40 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
                    stop_on_bio_stop: bool = True, cds_only: bool = False, termination_bias_enabled: bool = False,
                    termination_stop_bias: float = 0.0, termination_trigger_class_max: int = 0,
                    termination_bias_window: int = 0, multi_offset_prior_enabled: bool = False,
-                   attention_window: int | None = None) -> List[Tuple[List[int], Dict[str, int]]]:
+                   attention_window: int | None = None, token_sets=None, plans: Sequence[Sequence[int]] | None = None,
+                   end_with_plan: bool = False,
+                   with_logp: bool = False) -> List[Tuple[List[int], Dict[str, int]]]:
     """All contexts as one batch; returns [(ids, state)] in context order: ``ids`` = context +
-    generated tokens, ``state`` = the sequence's final cg_gen_state as a dict (state_record)."""
+    generated tokens, ``state`` = the sequence's final cg_gen_state as a dict (state_record).
+
+    ``token_sets`` (uint8 [n_sets][V]) and ``plans`` (per context, the set index of every generated
+    token; -1 or past the end = no set) give each step of each sequence its own allowed set; with
+    ``end_with_plan`` a sequence ends when its plan is used up (flag GEN_PLAN_END), and the batch
+    runs min(max_tokens, longest plan) steps.  ``with_logp`` adds ``logp_model`` (the sum of the
+    model's own log-probabilities of the drawn tokens) and ``logp_draw`` (under the distribution
+    drawn from) to every state dict.  Any of the four selects cg_sample_step_plan."""
     if multi_offset_prior_enabled:
         raise NotImplementedError("multi-offset priors need the ln_f history of the whole prefix; "
                                   "the batched generator does not keep it")
-    _check_fit(model, contexts, max_tokens)
+    planned = token_sets is not None or plans is not None or bool(end_with_plan) or bool(with_logp)
+    if planned:
+        plans = [[] for _ in contexts] if plans is None else [[int(s) for s in pl] for pl in plans]
+        if len(plans) != len(contexts):
+            raise ValueError("one plan per context")
+        if any(plans) and token_sets is None:
+            raise ValueError("plans need token_sets")
+        V = int(model.vocab_size)
+        sets = np.zeros((0, V), dtype=np.uint8) if token_sets is None else np.asarray(token_sets)
+        if sets.ndim != 2 or sets.dtype != np.uint8 or sets.shape[1] > V:
+            raise ValueError(f"token_sets is uint8 [n_sets][V <= {V}]")
+    if int(max_tokens) < 1:
+        raise ValueError("max_tokens must be at least 1")
+    if end_with_plan:
+        _check_fit_plans(model, contexts, plans)
+        steps = min(int(max_tokens), max(len(pl) for pl in plans))
+    else:
+        _check_fit(model, contexts, max_tokens)
+        steps = int(max_tokens)
     V = int(model.vocab_size)
     if len(itos) > V:
         raise ValueError(f"vocabulary of {len(itos)} tokens exceeds the model's {V}")
@@ -128,7 +237,7 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
     st[:, 6] = -1
     st[:, 7] = np.array(streams, dtype=np.uint64).astype(np.uint32).view(np.int32)
     state = torch.from_numpy(st).to(dev)
-    out_ids = torch.zeros(B, max_tokens, dtype=torch.int64, device=dev)
+    out_ids = torch.zeros(B, steps, dtype=torch.int64, device=dev)
     next_tok = torch.zeros(B, dtype=torch.int64, device=dev)
     pos = torch.zeros(B, dtype=torch.int32, device=dev)
     n_active = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -142,7 +251,7 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
     P.topk = int(topk or 0)
     P.target_codons = min(int(target_codons), INT_MAX)
     P.max_codons = min(int(max_codons), INT_MAX)
-    P.max_tokens = max_tokens
+    P.max_tokens = min(max_tokens, INT_MAX)
     P.require_terminal_stop = int(bool(require_terminal_stop))
     P.stop_on_eos = int(bool(stop_on_eos))
     P.stop_on_bio_stop = int(bool(stop_on_bio_stop))
@@ -152,6 +261,24 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
     P.n_term_classes = int(eng.cfg.termination_n_classes) if use_term else 0
     P.seed = int(seed) & 0xFFFFFFFF
     P.Tmax = cache.Tmax
+    if planned:
+        sets_full = np.zeros((sets.shape[0], V), dtype=np.uint8)
+        sets_full[:, :sets.shape[1]] = sets
+        plan_np = np.full((B, max(1, max(len(pl) for pl in plans))), -1, dtype=np.int32)
+        for b, pl in enumerate(plans):
+            plan_np[b, :len(pl)] = pl
+        sets_dev = torch.from_numpy(sets_full).to(dev)
+        plan_dev = torch.from_numpy(plan_np).to(dev)
+        plan_len = torch.tensor([len(pl) for pl in plans], dtype=torch.int32, device=dev)
+        logp = torch.zeros(B, 2, dtype=torch.float64, device=dev) if with_logp else None
+        PL = L.SamplePlan()
+        PL.n_sets = sets_full.shape[0]
+        if PL.n_sets:
+            PL.sets, PL.ld_sets = sets_dev.data_ptr(), sets_dev.stride(0)
+            PL.plan, PL.ld_plan = plan_dev.data_ptr(), plan_dev.stride(0)
+        PL.plan_len = plan_len.data_ptr()
+        PL.end_with_plan = int(bool(end_with_plan))
+        PL.logp = logp.data_ptr() if with_logp else None
 
     logits = cache.prefill(torch.from_numpy(idx).to(dev), torch.tensor(lens, dtype=torch.int32, device=dev),
                            window=attention_window, want_term=use_term)
@@ -159,11 +286,17 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
     ld_term = cache.term.stride(0) if use_term else 0
     stream = L.stream_ptr(dev)
     poll_every = max(1, int(poll_every))
-    for step in range(1, max_tokens + 1):
-        L.check(L.lib.cg_sample_step(C.byref(P), logits.data_ptr(), logits.stride(0), term_ptr, ld_term,
-                                     state.data_ptr(), next_tok.data_ptr(), out_ids.data_ptr(), out_ids.stride(0),
-                                     n_active.data_ptr(), B, stream), "cg_sample_step")
-        if step == max_tokens:  # the token cap has ended every sequence
+    for step in range(1, steps + 1):
+        if planned:
+            L.check(L.lib.cg_sample_step_plan(C.byref(P), C.byref(PL), logits.data_ptr(), logits.stride(0), term_ptr,
+                                              ld_term, state.data_ptr(), next_tok.data_ptr(), out_ids.data_ptr(),
+                                              out_ids.stride(0), n_active.data_ptr(), B, stream),
+                    "cg_sample_step_plan")
+        else:
+            L.check(L.lib.cg_sample_step(C.byref(P), logits.data_ptr(), logits.stride(0), term_ptr, ld_term,
+                                         state.data_ptr(), next_tok.data_ptr(), out_ids.data_ptr(),
+                                         out_ids.stride(0), n_active.data_ptr(), B, stream), "cg_sample_step")
+        if step == steps:  # the token cap, or the longest plan, has ended every sequence
             break
         if step % poll_every == 0 and int(n_active.item()) == 0:
             break
@@ -171,9 +304,12 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
         cache.decode(next_tok, pos, want_term=use_term)
     st = state.cpu().numpy()
     out = out_ids.cpu().numpy()
+    lp = logp.cpu().numpy() if planned and with_logp else None
     res = []
     for b, c in enumerate(contexts):
         rec = state_record(st[b])
+        if lp is not None:
+            rec["logp_model"], rec["logp_draw"] = float(lp[b, 0]), float(lp[b, 1])
         res.append((list(c) + [int(t) for t in out[b, :rec["n_tokens"]]], rec))
     return res
 
@@ -350,6 +486,50 @@ def batch_red_sampler(model, device, contexts: List[List[int]], stoi: Dict[str, 
     return solved, active, total
 
 
+def synonymous_info(ctx_len: int, ids: Sequence[int], target_protein: str, *, critic: bool = False,
+                    ebm: bool = False) -> Dict[str, object]:
+    """generate_cds_synonymous's info (generate.py:738-752)."""
+    return {
+        "protocol": "guided",
+        "guidance_components": ["synonymous_template", *(["ebm" if ebm else "critic"] if critic or ebm else [])],
+        "had_terminal_stop": True,
+        "early_stop": False,
+        "hit_hard_cap": False,
+        "target_codons": len(target_protein) + 1,
+        "generated_codons": len(target_protein) + 1,
+        "cds_only": True,
+        "require_terminal_stop": True,
+        "generated_tokens": len(ids) - int(ctx_len),
+    }
+
+
+def generate_cds_synonymous(model, critic_model, c_tokenizer, device, ctx_ids: List[int], stoi: Dict[str, int],
+                            itos: List[str], target_protein: str, alpha: float = 0.5, guide_top_k: int = 5,
+                            target_task: str = "stability", target_class_idx: int | None = None, ebm_model=None,
+                            temperature: float = 1.0, *, seed: int = 0,
+                            stream: int = 0) -> Tuple[List[int], Dict[str, object]]:
+    """A CDS that translates exactly to ``target_protein`` (generate.py:642-753): one draw per
+    residue among its synonymous codons (upper-cased; a residue without a codon in the vocabulary
+    draws among all codon tokens), then one among the stop codons, then <EOS_CDS> when the
+    vocabulary has it.  The stop rules are off; the sequence ends with its plan.  The temperature
+    applies to every draw, the stop codon's included.  Critic / EBM blending (alpha != 0 with a
+    critic or EBM model) needs the second model in the loop and is not part of the batched
+    generator."""
+    if (critic_model is not None or ebm_model is not None) and alpha != 0.0:
+        raise NotImplementedError("critic / EBM guided synonymous generation is outside the batched generator")
+    sets = TokenSets(stoi, itos, int(model.vocab_size))
+    plan = synonymous_plan(sets, target_protein)
+    (ids, _), = generate_batch(model, [list(ctx_ids)], stoi, itos, seed=seed, streams=[stream], max_tokens=INT_MAX,
+                               temperature=temperature, stop_on_eos=False, stop_on_bio_stop=False,
+                               token_sets=sets.array(), plans=[plan], end_with_plan=True)
+    eos = stoi.get("<EOS_CDS>")
+    if eos is not None:
+        ids = ids + [eos]
+    return ids, synonymous_info(len(ctx_ids), ids, target_protein, critic=critic_model is not None,
+                                ebm=ebm_model is not None)
+
+
 __all__ = ["generate_batch", "generate_model_raw", "generate_cds_constrained", "generate_cds_red",
-           "batch_red_sampler", "STOP_CODONS", "token_classes", "cds_mask", "raw_info", "constrained_info",
-           "state_record", "round_seed"]
+           "batch_red_sampler", "generate_cds_synonymous", "STOP_CODONS", "CODON_TABLE", "AA_TO_CODONS",
+           "TokenSets", "synonymous_plan", "synonymous_info", "translate", "token_classes", "cds_mask", "raw_info",
+           "constrained_info", "state_record", "round_seed"]

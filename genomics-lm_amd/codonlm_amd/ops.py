@@ -441,6 +441,23 @@ def sample_step(params, logits, state, next_tok, out_ids, n_active=None, term_lo
                                  L.stream_ptr(logits.device)), "cg_sample_step")
 
 
+def sample_step_plan(params, plan, logits, state, next_tok, out_ids, n_active=None, term_logits=None):
+    """cg_sample_step_plan in place: sample_step's arguments plus ``plan``, a _lib.SamplePlan whose
+    pointers the caller keeps alive (sets uint8 [n_sets][ld_sets], plan int32 [B][ld_plan], plan_len
+    int32 [B], logp fp64 [B][2], tok_logp fp32 [B][ld_tok_logp])."""
+    for t in (logits, state, next_tok, out_ids):
+        L.require_device(t, "sample_step_plan")
+    B = logits.shape[0]
+    if (logits.dtype != torch.float32 or state.dtype != torch.int32 or tuple(state.shape) != (B, 8)
+            or not state.is_contiguous() or next_tok.dtype != torch.int64 or out_ids.dtype != torch.int64):
+        raise ValueError("sample_step_plan: logits fp32 [B][V], state int32 [B][8], next_tok / out_ids int64")
+    L.check(L.lib.cg_sample_step_plan(C.byref(params), C.byref(plan) if plan is not None else None,
+                                      logits.data_ptr(), logits.stride(0), _p(term_logits),
+                                      term_logits.stride(0) if term_logits is not None else 0, state.data_ptr(),
+                                      next_tok.data_ptr(), out_ids.data_ptr(), out_ids.stride(0), _p(n_active), B,
+                                      L.stream_ptr(logits.device)), "cg_sample_step_plan")
+
+
 def gather_rows(src, sel, T):
     """cg_gather_rows with T > 0: out[b] = src[b*T + sel[b] - 1] for fp32 src [B*T][n] and a device
     int32 sel [B] of 1-based row counts (sel = T picks every sequence's last row)."""

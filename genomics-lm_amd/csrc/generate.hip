@@ -390,23 +390,42 @@ extern "C" int cg_row_head(int dtype, const void* xf, long long ldx, const float
 }
 
 // ===========================================================================
-// The fused sampler and stop-rule step (contract: include/codonlm_hip.h, cg_sample_step).
-// One workgroup per sequence, thread t owns tokens 4t .. 4t+3.  Weights, the top-k rank count
-// and the cumulative sums are fp64, so the drawn token is a function of the fp32 logits that a
-// double-precision restatement reproduces.
+// The fused sampler and stop-rule step (contract: include/codonlm_hip.h, cg_sample_step and
+// cg_sample_step_plan).  One workgroup per sequence, thread t owns tokens 4t .. 4t+3.  Weights,
+// the top-k rank count and the cumulative sums are fp64, so the drawn token is a function of the
+// fp32 logits that a double-precision restatement reproduces.
+//
+// PLAN = true is cg_sample_step_plan: the step's allowed set comes from the sequence's plan (four
+// adjacent bytes of the set row per thread, one block-wide OR for the empty-set fallback), the
+// raw logits' logsumexp rides on two more block reductions when a log-probability is wanted, and
+// thread 0 alone adds to the sequence's logp row.  PLAN = false compiles to cg_sample_step as it
+// was: every plan branch is an `if constexpr`.
 // ===========================================================================
 constexpr int SMP_V = 1024;
-__global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, const float* __restrict__ logits,
-                                                          long long ldl, const float* __restrict__ term,
-                                                          long long ld_term, cg_gen_state* __restrict__ state,
-                                                          int64_t* __restrict__ next_tok, int64_t* __restrict__ out_ids,
-                                                          long long ld_out, int32_t* __restrict__ n_active) {
+template <bool PLAN>
+__device__ __forceinline__ void sample_step_body(const cg_sample_params& P, const cg_sample_plan& PL,
+                                                 const float* __restrict__ logits, long long ldl,
+                                                 const float* __restrict__ term, long long ld_term,
+                                                 cg_gen_state* __restrict__ state, int64_t* __restrict__ next_tok,
+                                                 int64_t* __restrict__ out_ids, long long ld_out,
+                                                 int32_t* __restrict__ n_active) {
   __shared__ double w[SMP_V];
   __shared__ double red[256];
   __shared__ int s_bias, s_pick, s_last;
   const int b = blockIdx.x, tid = threadIdx.x, V = P.V;
   cg_gen_state st = state[b];
   if (st.flags & CG_GEN_DONE) return;
+  // the step's set: uniform over the workgroup (b and n_tokens are)
+  const uint8_t* set_row = nullptr;
+  int plen = 0;
+  if constexpr (PLAN) {
+    plen = PL.plan_len ? PL.plan_len[b] : 0;
+    const int j = st.n_tokens;
+    if (PL.n_sets > 0 && j >= 0 && j < plen && j < PL.ld_plan) {
+      const int s = PL.plan[(long long)b * PL.ld_plan + j];
+      if (s >= 0 && s < PL.n_sets) set_row = PL.sets + (long long)s * PL.ld_sets;
+    }
+  }
   // 1. termination bias
   if (tid == 0) {
     int apply = 0;
@@ -425,7 +444,22 @@ __global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, co
     s_pick = INT_MAX;
     s_last = -1;
   }
-  __syncthreads();
+  bool in_set[4] = {false, false, false, false};
+  bool use_set = false;
+  if constexpr (PLAN) {
+    int any = 0;
+    if (set_row) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int v = 4 * tid + k;
+        in_set[k] = v < V && set_row[v] != 0;
+        any |= in_set[k] ? 1 : 0;
+      }
+    }
+    use_set = __syncthreads_or(any) != 0;  // (also the barrier that publishes s_bias)
+  } else {
+    __syncthreads();
+  }
   const double bias = s_bias ? (double)P.stop_bias : 0.0;
   // 2./3. mask and weights
   double lv[4];
@@ -434,7 +468,10 @@ __global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, co
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int v = 4 * tid + k;
-    ok[k] = v < V && (!P.allowed || P.allowed[v]);
+    if constexpr (PLAN)
+      ok[k] = use_set ? in_set[k] : (v < V && (!P.allowed || P.allowed[v]));
+    else
+      ok[k] = v < V && (!P.allowed || P.allowed[v]);
     lv[k] = 0.0;
     if (ok[k]) {
       lv[k] = (double)logits[(long long)b * ldl + v] + ((P.tok_class[v] & CG_TOK_STOP) ? bias : 0.0);
@@ -449,6 +486,39 @@ __global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, co
   }
   mx = red[0];
   __syncthreads();
+  // logsumexp of the V raw logits (no bias, no mask, no temperature): thread 0 keeps it
+  double lse = 0.0;
+  if constexpr (PLAN) {
+    if (PL.logp || PL.tok_logp) {
+      double raw[4], rmx = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int v = 4 * tid + k;
+        raw[k] = v < V ? (double)logits[(long long)b * ldl + v] : -INFINITY;
+        rmx = fmax(rmx, raw[k]);
+      }
+      red[tid] = rmx;
+      __syncthreads();
+      for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = fmax(red[tid], red[tid + o]);
+        __syncthreads();
+      }
+      rmx = red[0];
+      __syncthreads();
+      double rs = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * tid + k < V) rs += exp(raw[k] - rmx);
+      red[tid] = rs;
+      __syncthreads();
+      for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+      }
+      lse = rmx + log(red[0]);
+      __syncthreads();
+    }
+  }
   const double temp = fmax(1e-6, (double)P.temperature);
   double wv[4];
 #pragma unroll
@@ -500,6 +570,18 @@ __global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, co
   // 6. record
   next_tok[b] = tok;
   if (out_ids && st.n_tokens < ld_out) out_ids[(long long)b * ld_out + st.n_tokens] = tok;
+  if constexpr (PLAN) {
+    if (PL.logp || PL.tok_logp) {
+      // a drawn token was kept by the top-k cut, so w[tok] is its weight under `total`
+      const double lp_model = (double)logits[(long long)b * ldl + tok] - lse;
+      if (PL.logp) {
+        PL.logp[2LL * b] += lp_model;
+        PL.logp[2LL * b + 1] += log(w[tok] / total);
+      }
+      if (PL.tok_logp && st.n_tokens >= 0 && st.n_tokens < PL.ld_tok_logp)
+        PL.tok_logp[(long long)b * PL.ld_tok_logp + st.n_tokens] = (float)lp_model;
+    }
+  }
   st.n_tokens++;
   const int cls = P.tok_class[tok];
   if (cls & CG_TOK_CODON) st.n_codons++;
@@ -519,6 +601,10 @@ __global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, co
   if (!(f & CG_GEN_DONE) && at_target && !P.require_terminal_stop) f |= CG_GEN_TARGET | CG_GEN_DONE;
   if (!(f & CG_GEN_DONE) && (st.n_codons >= P.max_codons || st.n_tokens >= P.max_tokens))
     f |= CG_GEN_CAP | CG_GEN_DONE;
+  if constexpr (PLAN) {
+    if (!(f & CG_GEN_DONE) && PL.end_with_plan && plen > 0 && st.n_tokens >= plen)
+      f |= CG_GEN_PLAN_END | CG_GEN_DONE;
+  }
   // 8. advance
   if (!(f & CG_GEN_DONE)) {
     st.pos = st.pos0 + st.n_tokens - 1;
@@ -531,6 +617,24 @@ __global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, co
   if (n_active && !(f & CG_GEN_DONE)) atomicAdd(n_active, 1);
 }
 
+__global__ __launch_bounds__(256) void sample_step_kernel(cg_sample_params P, const float* __restrict__ logits,
+                                                          long long ldl, const float* __restrict__ term,
+                                                          long long ld_term, cg_gen_state* __restrict__ state,
+                                                          int64_t* __restrict__ next_tok, int64_t* __restrict__ out_ids,
+                                                          long long ld_out, int32_t* __restrict__ n_active) {
+  sample_step_body<false>(P, cg_sample_plan{}, logits, ldl, term, ld_term, state, next_tok, out_ids, ld_out, n_active);
+}
+
+__global__ __launch_bounds__(256) void sample_step_plan_kernel(cg_sample_params P, cg_sample_plan PL,
+                                                               const float* __restrict__ logits, long long ldl,
+                                                               const float* __restrict__ term, long long ld_term,
+                                                               cg_gen_state* __restrict__ state,
+                                                               int64_t* __restrict__ next_tok,
+                                                               int64_t* __restrict__ out_ids, long long ld_out,
+                                                               int32_t* __restrict__ n_active) {
+  sample_step_body<true>(P, PL, logits, ldl, term, ld_term, state, next_tok, out_ids, ld_out, n_active);
+}
+
 extern "C" int cg_sample_step(const cg_sample_params* p, const float* logits, long long ldl, const float* term_logits,
                               long long ld_term, cg_gen_state* state, int64_t* next_tok, int64_t* out_ids,
                               long long ld_out, int32_t* n_active, int B, void* stream) {
@@ -540,6 +644,25 @@ extern "C" int cg_sample_step(const cg_sample_params* p, const float* logits, lo
   if (n_active && hipMemsetAsync(n_active, 0, 4, (hipStream_t)stream) != hipSuccess) return CG_ELAUNCH;
   hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, *p, logits, ldl, term_logits,
                      ld_term, state, next_tok, out_ids, ld_out, n_active);
+  CG_LAUNCH_CHECK();
+  return CG_OK;
+}
+
+extern "C" int cg_sample_step_plan(const cg_sample_params* p, const cg_sample_plan* plan, const float* logits,
+                                   long long ldl, const float* term_logits, long long ld_term, cg_gen_state* state,
+                                   int64_t* next_tok, int64_t* out_ids, long long ld_out, int32_t* n_active, int B,
+                                   void* stream) {
+  if (!p || !plan || !logits || !state || !next_tok || !p->tok_class || B <= 0 || p->V <= 0 || ldl < p->V)
+    return CG_EINVAL;
+  if (term_logits && ld_term < p->n_term_classes) return CG_EINVAL;
+  if (plan->n_sets < 0) return CG_EINVAL;
+  if (plan->n_sets > 0 &&
+      (!plan->sets || !plan->plan || !plan->plan_len || plan->ld_sets < p->V || plan->ld_plan < 0))
+    return CG_EINVAL;
+  if (p->V > SMP_V) return CG_EUNSUPPORTED;
+  if (n_active && hipMemsetAsync(n_active, 0, 4, (hipStream_t)stream) != hipSuccess) return CG_ELAUNCH;
+  hipLaunchKernelGGL(sample_step_plan_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, *p, *plan, logits, ldl,
+                     term_logits, ld_term, state, next_tok, out_ids, ld_out, n_active);
   CG_LAUNCH_CHECK();
   return CG_OK;
 }

@@ -642,6 +642,44 @@ int cg_sample_step(const cg_sample_params* p, const float* logits, long long ldl
                    long long ld_term, cg_gen_state* state, int64_t* next_tok, int64_t* out_ids, long long ld_out,
                    int32_t* n_active, int B, void* stream);
 
+/* cg_sample_step with a token set per step of every sequence and the log-probability of what it
+ * drew (ABI 0.6 addition; the reference's generate_cds_synonymous, generate.py :617-753, whose
+ * allowed set changes with every residue).  One workgroup per sequence; thread t reads the four
+ * adjacent bytes 4t .. 4t+3 of the step's set row.  For a sequence not yet CG_GEN_DONE, with
+ * j = n_tokens before the draw:
+ *  set choice: s = plan[b][j] when j < plan_len[b], otherwise none.  If 0 <= s < n_sets and
+ *     sets[s] allows at least one token < V (one block-wide OR), sets[s] replaces p->allowed in
+ *     step 2.  An empty set, or an s outside [0, n_sets), means p->allowed applies (the reference's
+ *     fallback, :675-676).  Steps 1 and 3-6 are cg_sample_step's, the draw the same u from
+ *     (seed, stream, n_tokens);
+ *  log-probabilities, fp64 from the fp32 logits, written by one thread of the sequence's own
+ *     workgroup (no floating-point atomics):
+ *       logp[b][0] += l_tok - logsumexp over all V raw logits: the model's own log-probability,
+ *                     no bias, no mask, no temperature;
+ *       logp[b][1] += log(w_tok / total) under the distribution drawn from, after bias, mask,
+ *                     temperature and top-k;
+ *       tok_logp[b][j] = the fp32 rounding of the first term, when j < ld_tok_logp;
+ *  stop rules: step 7 unchanged; after its last rule, if the sequence is not DONE, end_with_plan
+ *     is set, plan_len[b] > 0 and n_tokens >= plan_len[b]: CG_GEN_PLAN_END|DONE.  Steps 8-9
+ *     unchanged.
+ * A DONE sequence's state, next_tok, out_ids, logp and tok_logp rows are not touched.
+ * V > 1024: CG_EUNSUPPORTED.  A NULL plan struct, n_sets < 0, or with n_sets > 0 a NULL sets /
+ * plan / plan_len, ld_sets < V or ld_plan < 0: CG_EINVAL.  n_sets == 0 is plain sampling that can
+ * still report log-probabilities: sets and plan are not read, and a NULL plan_len counts as all
+ * zeros.  Plan entries at or past ld_plan are never read. */
+enum { CG_GEN_PLAN_END = 128 }; /* cg_gen_state.flags */
+typedef struct {
+  const uint8_t* sets; int n_sets; long long ld_sets; /* device [n_sets][ld_sets], ld_sets >= V; non-zero = allowed */
+  const int32_t* plan; long long ld_plan;             /* device [B][ld_plan]: plan[b][j] = set for generated token j */
+  const int32_t* plan_len;                            /* device [B], 0 <= plan_len[b] <= ld_plan */
+  int end_with_plan;                                  /* 1: a sequence ends when its plan is used up */
+  double* logp;                                       /* device [B][2], optional, += */
+  float* tok_logp; long long ld_tok_logp;             /* device [B][ld_tok_logp], optional */
+} cg_sample_plan;
+int cg_sample_step_plan(const cg_sample_params* p, const cg_sample_plan* plan, const float* logits, long long ldl,
+                        const float* term_logits, long long ld_term, cg_gen_state* state, int64_t* next_tok,
+                        int64_t* out_ids, long long ld_out, int32_t* n_active, int B, void* stream);
+
 /* Batched scoring (ABI 0.6 addition): one fused pass over fp32 logits rows [rows][ldl], of which
  * only the first V columns are read (V <= 1024, else CG_EUNSUPPORTED).  It replaces the
  * log_softmax / gather / F.cross_entropy passes of the reference's scoring scripts
@@ -724,7 +762,7 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
 /* sizeof the named ABI struct ("cg_gemm_desc", "cg_dw_product", "cg_dw_group", "cg_reduce_job",
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
- * "cg_score_desc"), 0 for
+ * "cg_score_desc", "cg_sample_plan"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -740,7 +778,8 @@ size_t cg_struct_bytes(const char* name);
  * the ragged decode entry points (cg_model_prefill_ragged, cg_model_decode_ragged,
  * cg_decode_ragged_workspace_bytes and their per-row ops, cg_attn_decode_ragged among them) and
  * cg_sample_step with cg_sample_params / cg_gen_state.  ABI 0.6, additions: batched scoring --
- * cg_score_rows with cg_score_desc, and cg_score_workspace. */
+ * cg_score_rows with cg_score_desc, and cg_score_workspace.  ABI 0.6, additions: per-step token
+ * sets and drawn-token log-probabilities -- cg_sample_step_plan with cg_sample_plan, CG_GEN_PLAN_END. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

@@ -165,6 +165,11 @@ class SamplePlan(C.Structure):
                 ("plan_len", vp), ("end_with_plan", i32), ("logp", vp), ("tok_logp", vp), ("ld_tok_logp", i64)]
 
 
+class OffsetPrior(C.Structure):
+    """cg_offset_prior: the offset heads of a step (indices into cfg.offsets) and their weights, in order"""
+    _fields_ = [("n", i32), ("head", i32 * 8), ("weight", f32 * 8)]
+
+
 class ScoreDesc(C.Structure):
     """cg_score_desc: every output pointer optional (None = not wanted)"""
     _fields_ = [("logits", vp), ("ldl", i64), ("rows", i32), ("V", i32), ("targets", vp), ("ignore_index", i32),
@@ -252,6 +257,11 @@ SIGNATURES = {
     "cg_segstate_step_ragged": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "cg_gather_rows": (i32, [vp, i64, vp, i32, i32, vp, i64, i32, vp, vp, i32, vp]),
     "cg_row_head": (i32, [i32, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
+    "cg_xf_hist_bytes": (sz, [C.POINTER(ModelCfg), i32, i32]),
+    "cg_model_prefill_hist": (i32, [C.POINTER(Model), vp, i32, i32, vp, i32, vp]),
+    "cg_model_decode_ragged_hist": (i32, [C.POINTER(Model), vp, vp, i32, vp, i32, vp, vp, sz, vp, vp, i64, vp, vp]),
+    "cg_offset_prior_workspace": (sz, [C.POINTER(ModelCfg), i32]),
+    "cg_offset_prior_add": (i32, [C.POINTER(Model), C.POINTER(OffsetPrior), vp, i32, vp, i32, vp, i64, vp, sz, vp]),
     "cg_sample_step": (i32, [C.POINTER(SampleParams), vp, i64, vp, i64, vp, vp, vp, i64, vp, i32, vp]),
     "cg_sample_step_plan": (i32, [C.POINTER(SampleParams), C.POINTER(SamplePlan), vp, i64, vp, i64, vp, vp, vp, i64, vp,
                                   i32, vp]),

@@ -263,8 +263,22 @@ class Engine:
     def new_kv_cache(self, B: int, Tmax: int | None = None) -> "KVCache":
         return KVCache(self, B, Tmax or self.cfg.block_size)
 
-    def new_ragged_kv_cache(self, B: int, Tmax: int | None = None) -> "RaggedKVCache":
-        return RaggedKVCache(self, B, Tmax or self.cfg.block_size)
+    def new_ragged_kv_cache(self, B: int, Tmax: int | None = None, xf_history: bool = False) -> "RaggedKVCache":
+        return RaggedKVCache(self, B, Tmax or self.cfg.block_size, xf_history=xf_history)
+
+    def offset_prior(self, weights) -> L.OffsetPrior:
+        """The cg_offset_prior of an ordered {offset: weight}: heads in the dict's order; a zero
+        weight and an offset the model has no head for are left out (they contribute nothing)."""
+        offs = [int(o) for o in self.cfg.multi_offset_targets][:8]
+        p = L.OffsetPrior()
+        for k, w in (weights or {}).items():
+            if float(w) == 0.0 or int(k) not in offs:
+                continue
+            if p.n >= 8:
+                raise ValueError("at most 8 offset priors")
+            p.head[p.n], p.weight[p.n] = offs.index(int(k)), float(w)
+            p.n += 1
+        return p
 
     def backward_phase(self, phase: int, layer: int = 0, accumulate: bool = False):
         st = L.stream_ptr(self.flat.device)
@@ -375,9 +389,13 @@ class RaggedKVCache:
     with the positions in a device int32 tensor.  A row whose position is negative (or >= Tmax)
     is inactive in that step: its cache rows, ``logits`` row and ``term`` row stay as they are.
     ``logits`` (B, V) and ``term`` (B, n_classes; models with a termination head) are fixed
-    buffers every step writes in place, so a generation loop holds no per-step allocations."""
+    buffers every step writes in place, so a generation loop holds no per-step allocations.
 
-    def __init__(self, engine: Engine, B: int, Tmax: int):
+    With ``xf_history`` the cache also keeps the ln_f output of every cached row (``hist``,
+    (B, Tmax, d) in the model dtype: cg_model_prefill_hist / cg_model_decode_ragged_hist), which is
+    what ``add_offset_priors`` (cg_offset_prior_add) reads."""
+
+    def __init__(self, engine: Engine, B: int, Tmax: int, xf_history: bool = False):
         cfg = engine.cfg
         if Tmax > cfg.block_size:
             raise ValueError("Tmax exceeds block_size")
@@ -391,6 +409,15 @@ class RaggedKVCache:
         self.logits = torch.zeros(self.B, cfg.vocab_size, dtype=torch.float32, device=dev)
         self.term = (torch.zeros(self.B, cfg.termination_n_classes, dtype=torch.float32, device=dev)
                      if cfg.termination_aux else None)
+        self.hist = self.prior_ws = None
+        if xf_history:
+            ccfg = engine.model.cfg
+            hb = int(L.lib.cg_xf_hist_bytes(C.byref(ccfg), self.B, self.Tmax))
+            hist = torch.zeros(max(hb, 1), dtype=torch.uint8, device=dev)
+            self.hist = hist[:hb].view(torch.bfloat16 if cfg.dtype == "bf16" else torch.float32).view(
+                self.B, self.Tmax, cfg.n_embd)
+            self.prior_ws = torch.zeros(max(int(L.lib.cg_offset_prior_workspace(C.byref(ccfg), self.B)), 1),
+                                        dtype=torch.uint8, device=dev)
 
     @torch.no_grad()
     def prefill(self, idx: torch.Tensor, lens: torch.Tensor, window: int | None = None, *,
@@ -413,6 +440,9 @@ class RaggedKVCache:
                                               int(window or 0), self.cache.data_ptr(), self.Tmax,
                                               self.seg.data_ptr(), self.logits.data_ptr(), L.stream_ptr(dev)),
                 "cg_model_prefill_ragged")
+        if self.hist is not None:
+            L.check(L.lib.cg_model_prefill_hist(C.byref(eng.model), lens.data_ptr(), B, T, self.hist.data_ptr(),
+                                                self.Tmax, L.stream_ptr(dev)), "cg_model_prefill_hist")
         if want_term:
             if self.term is None:
                 raise ValueError("the model has no termination head")
@@ -435,10 +465,35 @@ class RaggedKVCache:
         if want_term and self.term is None:
             raise ValueError("the model has no termination head")
         eng.sync_shadow()
-        L.check(L.lib.cg_model_decode_ragged(C.byref(eng.model), tok.data_ptr(), pos.data_ptr(), self.B,
-                                             self.cache.data_ptr(), self.Tmax, self.seg.data_ptr(),
-                                             self.ws.data_ptr(), self.ws.numel(), self.logits.data_ptr(),
-                                             self.term.data_ptr() if want_term else None,
-                                             self.term.stride(0) if want_term else 0,
-                                             L.stream_ptr(self.cache.device)), "cg_model_decode_ragged")
+        args = (C.byref(eng.model), tok.data_ptr(), pos.data_ptr(), self.B, self.cache.data_ptr(), self.Tmax,
+                self.seg.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.logits.data_ptr(),
+                self.term.data_ptr() if want_term else None, self.term.stride(0) if want_term else 0)
+        if self.hist is not None:
+            L.check(L.lib.cg_model_decode_ragged_hist(*args, self.hist.data_ptr(), L.stream_ptr(self.cache.device)),
+                    "cg_model_decode_ragged_hist")
+        else:
+            L.check(L.lib.cg_model_decode_ragged(*args, L.stream_ptr(self.cache.device)), "cg_model_decode_ragged")
+        return self.logits
+
+    def offset_prior(self, weights) -> L.OffsetPrior:
+        return self.eng.offset_prior(weights)
+
+    @torch.no_grad()
+    def add_offset_priors(self, pos: torch.Tensor, weights) -> torch.Tensor:
+        """``logits[b] += sum_k w_k * offset_logits[k][pos[b] + 1 - k]`` on the active rows, for the
+        heads of the ordered ``weights`` {offset: weight} (or a prepared cg_offset_prior) whose row
+        exists; ``pos[b]`` (int32, device) is sequence b's last cached row.  Returns ``logits``."""
+        if self.hist is None:
+            raise ValueError("the cache was built without xf_history")
+        if pos.dtype != torch.int32 or pos.numel() != self.B or not pos.is_contiguous():
+            raise ValueError("pos must be a contiguous int32 (B,)")
+        L.require_device(pos, "RaggedKVCache.add_offset_priors")
+        p = weights if isinstance(weights, L.OffsetPrior) else self.offset_prior(weights)
+        if p.n == 0:
+            return self.logits
+        self.eng.sync_shadow()
+        L.check(L.lib.cg_offset_prior_add(C.byref(self.eng.model), C.byref(p), self.hist.data_ptr(), self.Tmax,
+                                          pos.data_ptr(), self.B, self.logits.data_ptr(), self.logits.stride(0),
+                                          self.prior_ws.data_ptr(), self.prior_ws.numel(),
+                                          L.stream_ptr(self.cache.device)), "cg_offset_prior_add")
         return self.logits

@@ -14,8 +14,16 @@ are stated in include/codonlm_hip.h (cg_sample_step).
 ``generate_model_raw``, ``generate_cds_constrained``, ``generate_cds_red`` and
 ``batch_red_sampler`` take the reference's arguments (plus ``seed`` / ``stream``) and return the
 reference's ``info`` records.  The batched path does not slide the context window: prompt +
-token cap must fit block_size (``query_model.generate`` keeps the sliding loop).  Multi-offset
-priors and the critic-guided generator are not part of it.
+token cap must fit block_size (``query_model.generate`` keeps the sliding loop).  The
+critic-guided generator is not part of it.
+
+Multi-offset priors (``multi_offset_prior_enabled`` / ``multi_offset_prior_weights``, the
+reference's ``_apply_multi_offset_priors``): the cache keeps the ln_f output of every cached row
+(``new_ragged_kv_cache(..., xf_history=True)``) and, after the prefill and after every decode
+step, cg_offset_prior_add adds ``w_k * offset_logits[k][ctx_len - k]`` to the next-token logits
+in three launches for any number of heads; the sampler's termination bias, mask and temperature
+then act on the adjusted logits, as in the reference.  A model without offset heads raises
+NotImplementedError (the reference does nothing in that case).
 
 ``generate_cds_synonymous`` writes a CDS that translates to a given protein: with ``token_sets``
 and ``plans``, ``generate_batch`` goes through cg_sample_step_plan, where every generated token
@@ -169,8 +177,9 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
                    termination_stop_bias: float = 0.0, termination_trigger_class_max: int = 0,
                    termination_bias_window: int = 0, multi_offset_prior_enabled: bool = False,
                    attention_window: int | None = None, token_sets=None, plans: Sequence[Sequence[int]] | None = None,
-                   end_with_plan: bool = False,
-                   with_logp: bool = False) -> List[Tuple[List[int], Dict[str, int]]]:
+                   end_with_plan: bool = False, with_logp: bool = False,
+                   multi_offset_prior_weights: Dict[int, float] | None = None
+                   ) -> List[Tuple[List[int], Dict[str, int]]]:
     """All contexts as one batch; returns [(ids, state)] in context order: ``ids`` = context +
     generated tokens, ``state`` = the sequence's final cg_gen_state as a dict (state_record).
 
@@ -179,10 +188,15 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
     ``end_with_plan`` a sequence ends when its plan is used up (flag GEN_PLAN_END), and the batch
     runs min(max_tokens, longest plan) steps.  ``with_logp`` adds ``logp_model`` (the sum of the
     model's own log-probabilities of the drawn tokens) and ``logp_draw`` (under the distribution
-    drawn from) to every state dict.  Any of the four selects cg_sample_step_plan."""
-    if multi_offset_prior_enabled:
-        raise NotImplementedError("multi-offset priors need the ln_f history of the whole prefix; "
-                                  "the batched generator does not keep it")
+    drawn from) to every state dict.  Any of the four selects cg_sample_step_plan.
+
+    ``multi_offset_prior_enabled`` with ``multi_offset_prior_weights`` (an ordered {offset: weight})
+    adds the weighted offset-head logits to every step's logits before the sampler sees them."""
+    if multi_offset_prior_enabled and not getattr(model, "multi_offset_targets", None):
+        raise NotImplementedError("multi-offset priors need a model with offset heads (multi_offset_targets)")
+    if multi_offset_prior_enabled and with_logp:
+        raise ValueError("with_logp reports the model's own log-probability; it cannot be combined with "
+                         "multi-offset priors")
     planned = token_sets is not None or plans is not None or bool(end_with_plan) or bool(with_logp)
     if planned:
         plans = [[] for _ in contexts] if plans is None else [[int(s) for s in pl] for pl in plans]
@@ -242,7 +256,10 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
     pos = torch.zeros(B, dtype=torch.int32, device=dev)
     n_active = torch.zeros(1, dtype=torch.int32, device=dev)
 
-    cache = eng.new_ragged_kv_cache(B, int(model.block_size))
+    prior = eng.offset_prior(multi_offset_prior_weights) if multi_offset_prior_enabled else None
+    if prior is not None and prior.n == 0:  # no weights, zero weights, offsets without a head: nothing to add
+        prior = None
+    cache = eng.new_ragged_kv_cache(B, int(model.block_size), xf_history=prior is not None)
     P = L.SampleParams()
     P.V = V
     P.tok_class = tok_class.data_ptr()
@@ -282,6 +299,9 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
 
     logits = cache.prefill(torch.from_numpy(idx).to(dev), torch.tensor(lens, dtype=torch.int32, device=dev),
                            window=attention_window, want_term=use_term)
+    if prior is not None:
+        pos.copy_(state[:, 1] - 1)  # the last prompt row
+        cache.add_offset_priors(pos, prior)
     term_ptr = cache.term.data_ptr() if use_term else None
     ld_term = cache.term.stride(0) if use_term else 0
     stream = L.stream_ptr(dev)
@@ -302,6 +322,8 @@ def generate_batch(model, contexts: List[List[int]], stoi: Dict[str, int], itos:
             break
         pos.copy_(state[:, 1])
         cache.decode(next_tok, pos, want_term=use_term)
+        if prior is not None:
+            cache.add_offset_priors(pos, prior)
     st = state.cpu().numpy()
     out = out_ids.cpu().numpy()
     lp = logp.cpu().numpy() if planned and with_logp else None
@@ -370,7 +392,8 @@ def constrained_info(rec: Dict[str, int], *, target_codons: int, hard_cap: int, 
 
 def _constrained_batch(model, contexts, stoi, itos, target_codons, hard_cap, *, require_terminal_stop, temperature,
                        topk, termination_bias_enabled, termination_stop_bias, termination_trigger_class_max,
-                       termination_bias_window, cds_only, seed, streams, poll_every=16):
+                       termination_bias_window, cds_only, seed, streams, poll_every=16,
+                       multi_offset_prior_enabled=False, multi_offset_prior_weights=None):
     """generate_cds_constrained over a batch: the loop bound of generate.py:193 is the codon cap
     hard_cap and the token cap 3 * hard_cap."""
     res = generate_batch(model, contexts, stoi, itos, seed=seed, streams=streams, poll_every=poll_every,
@@ -380,11 +403,14 @@ def _constrained_batch(model, contexts, stoi, itos, target_codons, hard_cap, *, 
                          cds_only=cds_only, termination_bias_enabled=termination_bias_enabled,
                          termination_stop_bias=termination_stop_bias,
                          termination_trigger_class_max=termination_trigger_class_max,
-                         termination_bias_window=termination_bias_window)
+                         termination_bias_window=termination_bias_window,
+                         multi_offset_prior_enabled=multi_offset_prior_enabled,
+                         multi_offset_prior_weights=multi_offset_prior_weights)
     return [(ids, constrained_info(rec, target_codons=target_codons, hard_cap=hard_cap,
                                    require_terminal_stop=require_terminal_stop,
                                    termination_bias_enabled=termination_bias_enabled,
-                                   termination_bias_window=termination_bias_window, cds_only=cds_only))
+                                   termination_bias_window=termination_bias_window, cds_only=cds_only,
+                                   multi_offset_prior_enabled=multi_offset_prior_enabled))
             for ids, rec in res]
 
 
@@ -409,13 +435,14 @@ def generate_cds_constrained(model, device, ctx_ids: List[int], stoi: Dict[str, 
                              multi_offset_prior_weights: Dict[int, float] | None = None, *, seed: int = 0,
                              stream: int = 0) -> Tuple[List[int], Dict[str, object]]:
     """Generate codons up to the constraints and return (ids, info) (generate.py:153-290)."""
-    if multi_offset_prior_enabled:
-        raise NotImplementedError("multi-offset priors are outside the batched generator")
+    if multi_offset_prior_enabled and not getattr(model, "multi_offset_targets", None):
+        raise NotImplementedError("multi-offset priors need a model with offset heads (multi_offset_targets)")
     (ids, info), = _constrained_batch(
         model, [list(ctx_ids)], stoi, itos, target_codons, hard_cap, require_terminal_stop=require_terminal_stop,
         temperature=temperature, topk=topk, termination_bias_enabled=termination_bias_enabled,
         termination_stop_bias=termination_stop_bias, termination_trigger_class_max=termination_trigger_class_max,
-        termination_bias_window=termination_bias_window, cds_only=cds_only, seed=seed, streams=[stream])
+        termination_bias_window=termination_bias_window, cds_only=cds_only, seed=seed, streams=[stream],
+        multi_offset_prior_enabled=multi_offset_prior_enabled, multi_offset_prior_weights=multi_offset_prior_weights)
     return ids, info
 
 

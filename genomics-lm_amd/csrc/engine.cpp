@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/codonlm_hip.h"
+#include "offset_prior.h"
 
 extern "C" int cg_rope_tab(int dtype, void* qkv, long long ldqkv, int B, int T, int H, int KV, int hd,
                            const float* cos_tab, const float* sin_tab, int inverse, void* stream);
@@ -1513,9 +1514,11 @@ extern "C" int cg_model_prefill_ragged(cg_model* m, const int64_t* idx, const in
                         m->cfg.sep_id >= 0 ? C.A.seg : nullptr, segstate, B, C.s);
 }
 
-extern "C" int cg_model_decode_ragged(cg_model* m, const int64_t* tok, const int32_t* pos, int B, void* cache,
-                                      int Tmax, int32_t* segstate, void* dec_ws, size_t dec_ws_bytes, float* logits,
-                                      float* term_logits, long long ld_term, void* stream) {
+namespace {
+// one body for cg_model_decode_ragged (hist = nullptr: not one launch more) and its _hist form
+int decode_ragged_body(cg_model* m, const int64_t* tok, const int32_t* pos, int B, void* cache, int Tmax,
+                       int32_t* segstate, void* dec_ws, size_t dec_ws_bytes, float* logits, float* term_logits,
+                       long long ld_term, void* hist, void* stream) {
   if (!m || !tok || !pos || !cache || !segstate || !dec_ws || !logits || B <= 0) return CG_EINVAL;
   if (Tmax <= 0 || Tmax > m->cfg.block_size) return CG_EINVAL;
   if (m->cfg.dtype == CG_BF16 && !m->shadow) return CG_EINVAL;
@@ -1570,6 +1573,8 @@ extern "C" int cg_model_decode_ragged(cg_model* m, const int64_t* tok, const int
     }
   }
   CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, C.Lo.lnfw), P(C, C.Lo.lnfb), W.xf, d, W.mean, W.rstd, B, d, eps, C.s));
+  // the ln_f history: the active rows' new ln_f output -> hist[b][pos[b]]
+  if (hist) CK(cg_kv_append(C.dt, W.xf, d, hist, d, Tmax, pos, B, d, C.s));
   const long long hoff = m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head;
   cg_gemm_desc g = lin_fwd(C, W.xf, d, hoff, d, D.V, d, lg, D.V);
   g.c_dtype = CG_F32;
@@ -1578,6 +1583,83 @@ extern "C" int cg_model_decode_ragged(cg_model* m, const int64_t* tok, const int
   if (term_logits)
     CK(cg_row_head(C.dt, W.xf, d, P(C, C.Lo.termw), P(C, C.Lo.termb), pos, Tmax, B, d, nc, term_logits, ld_term, C.s));
   return CG_OK;
+}
+}  // namespace
+
+extern "C" int cg_model_decode_ragged(cg_model* m, const int64_t* tok, const int32_t* pos, int B, void* cache,
+                                      int Tmax, int32_t* segstate, void* dec_ws, size_t dec_ws_bytes, float* logits,
+                                      float* term_logits, long long ld_term, void* stream) {
+  return decode_ragged_body(m, tok, pos, B, cache, Tmax, segstate, dec_ws, dec_ws_bytes, logits, term_logits, ld_term,
+                            nullptr, stream);
+}
+
+// ===========================================================================
+// The ln_f history of a ragged batch and the multi-offset priors that read it
+// ===========================================================================
+extern "C" size_t cg_xf_hist_bytes(const cg_model_cfg* cfg, int B, int Tmax) {
+  Dims D;
+  if (!dims_of(cfg, D) || B <= 0 || Tmax <= 0) return 0;
+  return (size_t)B * Tmax * D.d * (cfg->dtype == CG_BF16 ? 2 : 4);
+}
+
+extern "C" int cg_model_prefill_hist(cg_model* m, const int32_t* len, int B, int T, void* hist, int Tmax,
+                                     void* stream) {
+  if (!m || !len || !hist || B <= 0 || T <= 0 || Tmax < T || Tmax > m->cfg.block_size) return CG_EINVAL;
+  if (m->B != B || m->T != T) return CG_EINVAL;  // the last forward is not that prefill
+  Ctx C;
+  CK(make_ctx(m, B, T, stream, C));
+  return cg_kv_scatter(C.dt, C.A.xf, C.D.d, T, hist, C.D.d, Tmax, len, B, C.D.d, C.s);
+}
+
+extern "C" int cg_model_decode_ragged_hist(cg_model* m, const int64_t* tok, const int32_t* pos, int B, void* cache,
+                                           int Tmax, int32_t* segstate, void* dec_ws, size_t dec_ws_bytes,
+                                           float* logits, float* term_logits, long long ld_term, void* hist,
+                                           void* stream) {
+  return decode_ragged_body(m, tok, pos, B, cache, Tmax, segstate, dec_ws, dec_ws_bytes, logits, term_logits, ld_term,
+                            hist, stream);
+}
+
+extern "C" size_t cg_offset_prior_workspace(const cg_model_cfg* cfg, int B) {
+  Dims D;
+  if (!dims_of(cfg, D) || B <= 0) return 0;
+  // u1 and u2, [8][B][d] each in the model dtype, on 256-byte boundaries
+  return 2 * (size_t)rup((long long)8 * B * D.d * (cfg->dtype == CG_BF16 ? 2 : 4), 256);
+}
+
+extern "C" int cg_offset_prior_add(cg_model* m, const cg_offset_prior* p, const void* hist, int Tmax,
+                                   const int32_t* pos, int B, float* logits, long long ldl, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  if (!m || !p || !hist || !pos || !logits || B <= 0) return CG_EINVAL;
+  if (p->n < 0 || p->n > 8) return CG_EINVAL;
+  const int noff = std::min(m->cfg.n_offsets, 8);
+  for (int i = 0; i < p->n; ++i)
+    if (p->head[i] < 0 || p->head[i] >= noff || m->cfg.offsets[p->head[i]] < 1) return CG_EINVAL;
+  if (ldl < m->cfg.vocab_size || Tmax < 1 || Tmax > m->cfg.block_size) return CG_EINVAL;
+  if (m->cfg.dtype == CG_BF16 && !m->shadow) return CG_EINVAL;
+  const size_t need = cg_offset_prior_workspace(&m->cfg, B);
+  if (need == 0 || !ws || ws_bytes < need) return CG_EINVAL;
+  if (p->n == 0) return CG_OK;
+  Ctx C;
+  CK(make_dec_ctx(m, B, stream, C));
+  cg_offprior_args a;
+  memset(&a, 0, sizeof(a));
+  a.dtype = C.dt;
+  a.n = p->n; a.B = B; a.d = C.D.d; a.V = C.D.V; a.Tmax = Tmax;
+  for (int i = 0; i < p->n; ++i) {
+    const int h = p->head[i];
+    a.offset[i] = m->cfg.offsets[h];
+    a.weight[i] = p->weight[i];
+    a.w1[i] = W(C, C.Lo.off1w[h]); a.b1[i] = P(C, C.Lo.off1b[h]);
+    a.w2[i] = W(C, C.Lo.off2w[h]); a.b2[i] = P(C, C.Lo.off2b[h]);
+  }
+  a.head = W(C, m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head);
+  a.hist = hist;
+  a.pos = pos;
+  a.u1 = ws;
+  a.u2 = (char*)ws + need / 2;
+  a.logits = logits;
+  a.ldl = ldl;
+  return cg_offset_prior_stages(&a, C.s);
 }
 
 extern "C" size_t cg_struct_bytes(const char* name) {
@@ -1588,7 +1670,7 @@ extern "C" size_t cg_struct_bytes(const char* name) {
   CG_SZ(cg_gemm_desc) CG_SZ(cg_dw_product) CG_SZ(cg_dw_group) CG_SZ(cg_reduce_job) CG_SZ(cg_reduce_batch)
   CG_SZ(cg_transpose_item) CG_SZ(cg_transpose_batch) CG_SZ(cg_adamw_segment) CG_SZ(cg_model_cfg)
   CG_SZ(cg_param_entry) CG_SZ(cg_model) CG_SZ(cg_model_opts) CG_SZ(cg_sample_params) CG_SZ(cg_gen_state)
-  CG_SZ(cg_score_desc) CG_SZ(cg_sample_plan)
+  CG_SZ(cg_score_desc) CG_SZ(cg_sample_plan) CG_SZ(cg_offset_prior)
 #undef CG_SZ
   return 0;
 }

@@ -589,6 +589,37 @@ int cg_gather_rows(const float* src, long long lds, const int32_t* sel, int T, i
 int cg_row_head(int dtype, const void* xf, long long ldx, const float* w, const float* bias, const int32_t* pos,
                 int Tmax, int B, int d, int nc, float* out, long long ldo, void* stream);
 
+/* Multi-offset priors in batched generation (ABI 0.6; the reference's generate.py :130-150,
+ * :203-212): the offset head k of a step reads the ln_f output of cache row ctx_len - k, so the
+ * ragged decode keeps that output per row.
+ * ln_f history of a ragged batch: [B][Tmax][d] in the model dtype, row t of sequence b = the
+ * ln_f output of cache row t.  cg_xf_hist_bytes = B*Tmax*d*elem (0 for B <= 0). */
+size_t cg_xf_hist_bytes(const cg_model_cfg* cfg, int B, int Tmax);
+/* after cg_model_prefill_ragged (same m, B, T): hist[b][t] = ln_f row b*T+t for t < len[b] */
+int cg_model_prefill_hist(cg_model* m, const int32_t* len, int B, int T, void* hist, int Tmax, void* stream);
+/* cg_model_decode_ragged, and the new row's ln_f output appended at hist[b][pos[b]] on the
+ * active rows (one cg_kv_append more).  hist NULL = exactly cg_model_decode_ragged. */
+int cg_model_decode_ragged_hist(cg_model* m, const int64_t* tok, const int32_t* pos, int B, void* cache, int Tmax,
+                                int32_t* segstate, void* dec_ws, size_t dec_ws_bytes, float* logits,
+                                float* term_logits, long long ld_term, void* hist, void* stream);
+typedef struct { int n; int head[8]; float weight[8]; } cg_offset_prior; /* head[i] indexes cfg.offsets */
+size_t cg_offset_prior_workspace(const cg_model_cfg* cfg, int B);
+/* For every active row (0 <= pos[b] < Tmax; pos[b] = the last cached row, so ctx_len = pos[b]+1),
+ * for i = 0..n-1 in this order: k = cfg.offsets[head[i]], src = pos[b] + 1 - k; if weight[i] != 0
+ * and src >= 0:  logits[b][0..V) += weight[i] * head(W2_k gelu(W1_k hist[b][src] + b1_k) + b2_k).
+ * Inactive rows, rows no head applies to and columns >= V are not touched.  `head` is the decode
+ * step's linear (tied or not, no bias).  Three launches whatever n is (all W1 products, all W2
+ * products, the head products with the weighted sum); one owner per logits element, no atomics,
+ * every dot product in a fixed order that does not depend on B: a row's result is bitwise the
+ * same alone and in any batch.  fp32: exact FMA chains; bf16: the operand rounding of
+ * cg_model_aux_forward (shadow weights, bf16 activations, fp32 accumulation and logits).
+ * CG_EINVAL: a NULL m / p / hist / pos / logits / ws, B <= 0, n outside 0..8, a head[i] outside
+ * [0, cfg.n_offsets) or with an offset < 1, ldl < V, Tmax outside 1..block_size, ws_bytes below
+ * cg_offset_prior_workspace(cfg, B), bf16 without the shadow weights.  n == 0: CG_OK, no launch.
+ * CG_EUNSUPPORTED: n_embd above 4864 (a workgroup keeps its 8 x n_embd fp32 weight slice in LDS). */
+int cg_offset_prior_add(cg_model* m, const cg_offset_prior* p, const void* hist, int Tmax, const int32_t* pos,
+                        int B, float* logits, long long ldl, void* ws, size_t ws_bytes, void* stream);
+
 /* The fused sampler and stop-rule step of batched generation (ABI 0.6; the rules of the
  * reference's generate.py :51-59, :111-127, :193-260): one launch per generated token, one
  * workgroup per sequence, V <= 1024 (else CG_EUNSUPPORTED).  tok_class[v] is a bit set of
@@ -762,7 +793,7 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
 /* sizeof the named ABI struct ("cg_gemm_desc", "cg_dw_product", "cg_dw_group", "cg_reduce_job",
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
- * "cg_score_desc", "cg_sample_plan"), 0 for
+ * "cg_score_desc", "cg_sample_plan", "cg_offset_prior"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -779,7 +810,10 @@ size_t cg_struct_bytes(const char* name);
  * cg_decode_ragged_workspace_bytes and their per-row ops, cg_attn_decode_ragged among them) and
  * cg_sample_step with cg_sample_params / cg_gen_state.  ABI 0.6, additions: batched scoring --
  * cg_score_rows with cg_score_desc, and cg_score_workspace.  ABI 0.6, additions: per-step token
- * sets and drawn-token log-probabilities -- cg_sample_step_plan with cg_sample_plan, CG_GEN_PLAN_END. */
+ * sets and drawn-token log-probabilities -- cg_sample_step_plan with cg_sample_plan, CG_GEN_PLAN_END.
+ * ABI 0.6, additions: multi-offset priors in batched generation -- cg_xf_hist_bytes,
+ * cg_model_prefill_hist, cg_model_decode_ragged_hist, cg_offset_prior_workspace and
+ * cg_offset_prior_add with cg_offset_prior. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

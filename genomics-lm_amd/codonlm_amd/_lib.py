@@ -178,6 +178,15 @@ class ScoreDesc(C.Structure):
                 ("seq_logp", vp), ("seq_count", vp), ("acc", vp), ("workspace", vp), ("ws_bytes", sz)]
 
 
+ATTR_LOGPROB, ATTR_LOGIT = 0, 1  # cg_attr_seed / cg_attr_desc.mode
+
+
+class AttrDesc(C.Structure):
+    """cg_attr_desc: the seed (y None = the forward's own loss) and the optional outputs"""
+    _fields_ = [("y", vp), ("w", vp), ("mode", i32), ("gxt", vp), ("gxi", vp), ("gnorm", vp),
+                ("dx0", vp), ("ld_dx0", i64)]
+
+
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {
     "cg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -267,6 +276,9 @@ SIGNATURES = {
                                   i32, vp]),
     "cg_score_workspace": (sz, [i32]),
     "cg_score_rows": (i32, [C.POINTER(ScoreDesc), vp]),
+    "cg_attr_seed": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
+    "cg_attr_reduce": (i32, [vp, i64, vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
+    "cg_model_input_grad": (i32, [C.POINTER(Model), C.POINTER(AttrDesc), vp]),
     "cg_model_hidden": (vp, [C.POINTER(Model), i32, C.POINTER(i32), C.POINTER(i64)]),
     "cg_model_attn_probs": (i32, [C.POINTER(Model), i32, vp, vp]),
     "cg_probe_enable": (i32, [i32]),

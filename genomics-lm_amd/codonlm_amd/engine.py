@@ -184,6 +184,7 @@ class Engine:
         if targets is not None and loss is None:
             loss = torch.empty((), dtype=torch.float32, device=dev)
         self._idx, self._targets = idx, targets  # keep alive for backward
+        self._dlogits_seeded = False  # the fused cross-entropy's dlogits are the loss's again
         st = L.stream_ptr(dev)
         L.check(L.lib.cg_model_forward(C.byref(self.model), idx.data_ptr(),
                                        targets.data_ptr() if targets is not None else None,
@@ -302,6 +303,58 @@ class Engine:
         self.backward_phase(2, 0, accumulate)
         if bucket_hook:
             bucket_hook("embed")
+
+    @torch.no_grad()
+    def input_grad(self, y=None, w=None, mode: str = "logprob", want=("gxt", "gxi", "gnorm"), dx0: bool = False):
+        """cg_model_input_grad of the last forward, which must have been an eval forward: the
+        gradient of a seeded objective at the embedding output and its per-token reductions, as an
+        ops.AttrResult of (B, T) tensors (``dx0`` (B, T, d) when asked for).  ``y`` int64 (B, T):
+        the objective is sum w log p(y) over the positions with 0 <= y < V (``mode`` "logprob";
+        "logit": the weighted logits), ``w`` fp32 (B, T) or None = 1.  ``y`` None: the loss of the
+        forward itself (it must have had targets) -- its mean cross-entropy with the model's
+        smoothing and class weights.  Writes no parameter gradient."""
+        from . import ops
+        m = self.model
+        B, T, d = m.B, m.T, self.cfg.n_embd
+        if B <= 0 or T <= 0:
+            raise ValueError("input_grad: no forward has run")
+        if mode not in ops.ATTR_MODES:
+            raise ValueError(f"input_grad: mode is one of {sorted(ops.ATTR_MODES)}")
+        unknown = set(want) - set(ops.ATTR_OUTPUTS)
+        if unknown:
+            raise ValueError(f"input_grad: unknown outputs {sorted(unknown)}")
+        dev = self.flat.device
+        a = L.AttrDesc()
+        a.mode = ops.ATTR_MODES[mode]
+        keep = []
+        if y is None:
+            if w is not None:
+                raise ValueError("input_grad: w needs y")
+            if getattr(self, "_dlogits_seeded", False):
+                raise ValueError("input_grad: a seeded call replaced the forward's loss gradient; run the forward again")
+        else:
+            for name, t, dt in (("y", y, torch.int64), ("w", w, torch.float32)):
+                if t is None:
+                    continue
+                L.require_device(t, "input_grad")
+                if t.numel() != B * T:
+                    raise ValueError(f"input_grad: {name} has one entry per position of the forward, ({B}, {T})")
+                t = t.reshape(-1).to(dtype=dt).contiguous()
+                keep.append(t)
+                setattr(a, name, t.data_ptr())
+        res = ops.AttrResult()
+        for name in ops.ATTR_OUTPUTS:
+            if name in want:
+                t = torch.empty(B, T, dtype=torch.float32, device=dev)
+                setattr(res, name, t)
+                setattr(a, name, t.data_ptr())
+        if dx0:
+            res.dx0 = torch.empty(B, T, d, dtype=torch.float32, device=dev)
+            a.dx0, a.ld_dx0 = res.dx0.data_ptr(), d
+        L.check(L.lib.cg_model_input_grad(C.byref(m), C.byref(a), L.stream_ptr(dev)), "cg_model_input_grad")
+        if y is not None:
+            self._dlogits_seeded = True  # until the next forward
+        return res
 
     def attn_probs(self, layer: int) -> torch.Tensor:
         """Attention probabilities of block `layer` of the last forward: fp32 (B, H, T, T)."""

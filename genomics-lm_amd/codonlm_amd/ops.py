@@ -547,6 +547,87 @@ def score_rows(logits, targets=None, *, V=None, ignore_index=0, smoothing=0.0, s
     return res
 
 
+ATTR_MODES = {"logprob": L.ATTR_LOGPROB, "logit": L.ATTR_LOGIT}
+
+
+def attr_seed(logits, y, w=None, *, V=None, mode="logprob", pad_to=None, split=False):
+    """cg_attr_seed over fp32 logits [rows][ld] (the first ``V`` columns of a row are read): the
+    gradient of sum_r w[r] log p(y[r]) (``mode`` "logprob") or of sum_r w[r] z[r][y[r]] ("logit")
+    with respect to the logits, fp32 [rows][pad_to or V] -- or, with ``split`` (CG_BF16X2), bf16
+    [rows][pad_to] with hi at column c and lo at column pad_to/2 + c (pad_to even, pad_to/2 >= V).
+    ``y`` int64 [rows] and ``w`` fp32 [rows] (None = 1) live on the device; a row with y outside
+    [0, V) or w == 0 is all zero, and so are the pad columns."""
+    L.require_device(logits, "attr_seed")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[0] and logits.stride(1) != 1):
+        raise ValueError("attr_seed: logits is fp32 [rows][ld] with contiguous rows")
+    if mode not in ATTR_MODES:
+        raise ValueError(f"attr_seed: mode is one of {sorted(ATTR_MODES)}")
+    rows = logits.shape[0]
+    V = logits.shape[1] if V is None else int(V)
+    dev = logits.device
+    L.require_device(y, "attr_seed")
+    y = y.reshape(-1).to(torch.int64).contiguous()
+    if y.numel() != rows:
+        raise ValueError("attr_seed: one class per row")
+    if w is not None:
+        L.require_device(w, "attr_seed")
+        w = w.reshape(-1).to(torch.float32).contiguous()
+        if w.numel() != rows:
+            raise ValueError("attr_seed: one weight per row")
+    ldd = int(pad_to) if pad_to else (2 * V if split else V)
+    out = torch.empty(rows, ldd, dtype=torch.bfloat16 if split else torch.float32, device=dev)
+    L.check(L.lib.cg_attr_seed(logits.data_ptr(), logits.stride(0) if rows else V, y.data_ptr(), _p(w), rows, V,
+                               ATTR_MODES[mode], L.CG_BF16X2 if split else L.CG_F32, out.data_ptr(), ldd,
+                               L.stream_ptr(dev)), "cg_attr_seed")
+    return out
+
+
+class AttrResult:
+    """Device tensors of one attr_reduce / Engine.input_grad call; an output that was not asked for
+    is None."""
+    __slots__ = ("gxt", "gxi", "gnorm", "dx0")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
+ATTR_OUTPUTS = ("gxt", "gxi", "gnorm")
+
+
+def attr_reduce(g, idx, tok_emb=None, x0=None, *, want=ATTR_OUTPUTS):
+    """cg_attr_reduce of an input gradient ``g`` fp32 [rows][d] (row stride >= d): an AttrResult with
+    ``gxt`` = g . tok_emb[idx] (0 where idx is outside the table), ``gxi`` = g . x0 and ``gnorm`` =
+    |g|, fp32 [rows] each, for the outputs named in ``want``.  ``idx`` int64 [rows], ``tok_emb`` fp32
+    [V][>= d] and ``x0`` fp32 [rows][>= d] live on the device."""
+    L.require_device(g, "attr_reduce")
+    unknown = set(want) - set(ATTR_OUTPUTS)
+    if unknown:
+        raise ValueError(f"attr_reduce: unknown outputs {sorted(unknown)}")
+    for name, t in (("g", g), ("tok_emb", tok_emb), ("x0", x0)):
+        if t is not None and (t.dim() != 2 or t.dtype != torch.float32 or (t.shape[0] and t.stride(1) != 1)):
+            raise ValueError(f"attr_reduce: {name} is fp32 [rows][ld] with contiguous rows")
+    rows, d = g.shape
+    L.require_device(idx, "attr_reduce")
+    idx = idx.reshape(-1).to(torch.int64).contiguous()
+    if idx.numel() != rows:
+        raise ValueError("attr_reduce: one token id per row")
+    if "gxt" in want and (tok_emb is None or tok_emb.shape[1] != d):
+        raise ValueError("attr_reduce: gxt needs tok_emb [V][d]")
+    if "gxi" in want and (x0 is None or tuple(x0.shape) != (rows, d)):
+        raise ValueError("attr_reduce: gxi needs x0 [rows][d]")
+    res = AttrResult()
+    for name in ATTR_OUTPUTS:
+        if name in want:
+            setattr(res, name, torch.empty(rows, dtype=torch.float32, device=g.device))
+    L.check(L.lib.cg_attr_reduce(g.data_ptr(), g.stride(0) if rows else d, idx.data_ptr(), _p(tok_emb),
+                                 tok_emb.stride(0) if tok_emb is not None else 0,
+                                 tok_emb.shape[0] if tok_emb is not None else 0, _p(x0),
+                                 x0.stride(0) if x0 is not None and rows else d, rows, d, _p(res.gxt), _p(res.gxi),
+                                 _p(res.gnorm), L.stream_ptr(g.device)), "cg_attr_reduce")
+    return res
+
+
 def attn_probs(qkv, segstart, lse, B, T, H, KV, hd, window=0):
     """softmax(QK^T / sqrt(hd)) on the visible (query, key) pairs from the forward's qkv rows and
     LSE, 0 elsewhere: fp32 [B][H][T][T]."""

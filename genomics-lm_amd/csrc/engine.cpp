@@ -1293,6 +1293,93 @@ extern "C" int cg_model_backward(cg_model* m, int phase, int layer, int accumula
   return CG_EINVAL;
 }
 
+// Input attribution (scripts/analyze_saliency.py:48-81): the gradient of a seeded objective at the
+// embedding output of the last eval forward and its per-token reductions.  The dX chain of
+// cg_model_backward alone, with the same kernels and operands: no dW product, no bias column sum,
+// no parameter reduction, no embedding scatter, nothing written to m->grads or to the model's
+// backward state.  No block's operands outlive the block here, so slot 0 serves every block.
+extern "C" int cg_model_input_grad(cg_model* m, const cg_attr_desc* a, void* stream) {
+  if (!m || !a || !m->idx || m->B <= 0 || m->T <= 0 || m->training) return CG_EINVAL;
+  if (a->y ? (a->mode != CG_ATTR_LOGPROB && a->mode != CG_ATTR_LOGIT) : !m->targets) return CG_EINVAL;
+  if (a->dx0 && a->ld_dx0 < m->cfg.n_embd) return CG_EINVAL;
+  if (m->cfg.dtype == CG_BF16 && !m->shadow) return CG_EINVAL;
+  if (m->cfg.use_rope && (!m->rope_cos || !m->rope_sin)) return CG_EINVAL;
+  Ctx C;
+  CK(make_ctx(m, m->B, m->T, stream, C));
+  const Dims& D = C.D;
+  const Acts& A = C.A;
+  const int d = D.d;
+  const long long M = C.M;
+  const DwSlot& sl = A.slot[0];
+  CK(transpose_weights(C));
+  const long long hoff = m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head;
+  CK(fill_head2(C, hoff));
+  if (a->y)
+    CK(cg_attr_seed(A.logits_pad, D.Vp, a->y, a->w, (int)M, D.V, a->mode, C.dt == CG_BF16 ? CG_BF16X2 : CG_F32,
+                    A.dlogits, A.ldl, C.s));
+  // dxf = dlogits . E, then ln_f backward: A.g = dL/d(x_L), its compute-dtype copy to block L-1's MLP
+  cg_gemm_desc g = head_dx(C, hoff, A.dtmp, d);
+  g.c_dtype = CG_F32;
+  CK(cg_gemm(&g, C.s));
+  CK(cg_layernorm_bwd_partials(CG_F32, A.dtmp, d, A.x + (size_t)D.L * M * d, d, A.meanf, A.rstdf, P(C, C.Lo.lnfw),
+                               nullptr, A.g, C.dt, D.L > 0 ? sl.gin : nullptr, 0, 0.f, A.lnpart, A.nb.lnp, 0, (int)M,
+                               d, C.s));
+  const void* segp = m->cfg.sep_id >= 0 ? A.seg : nullptr;
+  const bool rope_in = D.rope && !m->cfg.opts.rope_tables;  // the inverse rotation inside the kernels
+  for (int l = D.L - 1; l >= 0; --l) {
+    const auto& o = C.Lo.lay[l];
+    const auto& la = A.la[l];
+    // MLP branch: sl.gin = dL/d(mlp out) -> A.dsmall = dL/d(ln2 out)
+    if (!D.swiglu) {
+      g = lin_dx(C, sl.gin, d, o.w2, D.hid, d, D.hid, sl.dmlp, D.hid, la.w2T);
+      g.epilogue = CG_EPI_DGELU | CG_EPI_GELU_DERIV; g.aux = la.a; g.ld_aux = D.hid;
+      CK(cg_gemm(&g, C.s));
+      g = lin_dx(C, sl.dmlp, D.hid, o.w1, d, D.hid, d, A.dsmall, d, la.w1T);
+      CK(cg_gemm(&g, C.s));
+    } else {
+      g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, sl.dmlp, 2 * D.Hp, la.wdT);
+      g.epilogue = CG_EPI_DSWIGLU; g.aux = la.gu; g.ld_aux = 2 * D.Hp; g.n_valid = D.hid;
+      int rc = C.dt == CG_BF16 ? cg_gemm(&g, C.s) : CG_EUNSUPPORTED;
+      if (rc == CG_EUNSUPPORTED) {
+        g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, A.dsmall, D.Hp, la.wdT);
+        CK(cg_gemm(&g, C.s));
+        rc = cg_swiglu_bwd(C.dt, la.gu, 2 * D.Hp, D.Hp, A.dsmall, D.Hp, sl.dmlp, 2 * D.Hp, (int)M, D.hid, C.s);
+      }
+      CK(rc);
+      g = lin_dx(C, sl.dmlp, 2 * D.Hp, o.wgu, d, 2 * D.Hp, d, A.dsmall, d, la.wguT);
+      CK(cg_gemm(&g, C.s));
+    }
+    CK(cg_layernorm_bwd_partials(C.dt, A.dsmall, d, la.xmid, d, la.mean2, la.rstd2, P(C, o.ln2w), A.g, A.g, C.dt,
+                                 sl.gattn, 0, 0.f, sl.lnp2, A.nb.lnp, 0, (int)M, d, C.s));
+    // attention branch: sl.gattn = dL/d(proj out) -> A.dsmall = dL/d(ln1 out)
+    g = lin_dx(C, sl.gattn, d, o.wp, d, d, d, A.dsmall, d, la.pT);
+    CK(cg_gemm(&g, C.s));
+    int rc = CG_EUNSUPPORTED;
+    if (!D.rope || rope_in)
+      rc = cg_attn_bwd_algo(m->cfg.opts.attn_bwd_algo, C.dt, la.qkv, D.Nqkv, (const int32_t*)segp, la.y, d, A.dsmall,
+                            d, la.lse, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->window, 0, 0.f, nullptr, nullptr,
+                            0, rope_in ? m->rope_cos : nullptr, rope_in ? m->rope_sin : nullptr, A.delta, A.nb.delta,
+                            C.s);
+    if (rc == CG_EUNSUPPORTED) {
+      rc = cg_attn_bwd(C.dt, la.qkv, D.Nqkv, (const int32_t*)segp, la.y, d, A.dsmall, d, la.lse, sl.dqkv, D.Nqkv, C.B,
+                       C.T, D.H, D.KV, D.hd, m->window, 0, 0.f, nullptr, nullptr, 0, A.delta, A.nb.delta, C.s);
+      if (rc == CG_OK && D.rope)
+        rc = cg_rope_tab(C.dt, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->rope_cos, m->rope_sin, 1, C.s);
+    }
+    CK(rc);
+    g = lin_dx(C, sl.dqkv, D.Nqkv, o.wqkv, d, D.Nqkv, d, A.dsmall, d, la.qkvT);
+    CK(cg_gemm(&g, C.s));
+    CK(cg_layernorm_bwd_partials(C.dt, A.dsmall, d, A.x + (size_t)l * M * d, d, la.mean1, la.rstd1, P(C, o.ln1w), A.g,
+                                 A.g, C.dt, l > 0 ? sl.gin : nullptr, 0, 0.f, sl.lnp1, A.nb.lnp, 0, (int)M, d, C.s));
+  }
+  if (a->gxt || a->gxi || a->gnorm)
+    CK(cg_attr_reduce(A.g, d, m->idx, P(C, C.Lo.tok), d, D.V, A.x, d, (int)M, d, a->gxt, a->gxi, a->gnorm, C.s));
+  if (a->dx0 && hipMemcpy2DAsync(a->dx0, (size_t)a->ld_dx0 * 4, A.g, (size_t)d * 4, (size_t)d * 4, (size_t)M,
+                                 hipMemcpyDeviceToDevice, C.s) != hipSuccess)
+    return CG_ELAUNCH;
+  return CG_OK;
+}
+
 // attention probabilities of block `layer` of the last forward (fp32 [B][H][T][T])
 extern "C" int cg_model_attn_probs(const cg_model* m, int layer, float* out, void* stream) {
   if (!m || !out) return CG_EINVAL;
@@ -1670,7 +1757,7 @@ extern "C" size_t cg_struct_bytes(const char* name) {
   CG_SZ(cg_gemm_desc) CG_SZ(cg_dw_product) CG_SZ(cg_dw_group) CG_SZ(cg_reduce_job) CG_SZ(cg_reduce_batch)
   CG_SZ(cg_transpose_item) CG_SZ(cg_transpose_batch) CG_SZ(cg_adamw_segment) CG_SZ(cg_model_cfg)
   CG_SZ(cg_param_entry) CG_SZ(cg_model) CG_SZ(cg_model_opts) CG_SZ(cg_sample_params) CG_SZ(cg_gen_state)
-  CG_SZ(cg_score_desc) CG_SZ(cg_sample_plan) CG_SZ(cg_offset_prior)
+  CG_SZ(cg_score_desc) CG_SZ(cg_sample_plan) CG_SZ(cg_offset_prior) CG_SZ(cg_attr_desc)
 #undef CG_SZ
   return 0;
 }

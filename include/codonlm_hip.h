@@ -757,6 +757,70 @@ typedef struct {
 size_t cg_score_workspace(int rows);
 int cg_score_rows(const cg_score_desc* d, void* stream);
 
+/* Input attribution (ABI 0.6 addition): gradient x input saliency and per-target dependency maps
+ * on the native engine.  Replaces the tok_emb forward hook + retain_grad() + loss.backward() of the
+ * reference's scripts/analyze_saliency.py :48-81, whose only use of the backward is the gradient at
+ * the embedding output: cg_model_input_grad runs the dX chain alone, from a caller-chosen seed.
+ *
+ * cg_attr_seed: d(objective)/d(logits) of rows of fp32 logits [rows][ldl] (V used columns), written
+ * in the engine's dlogits layouts: d_dtype CG_F32 [rows][ldd], ldd >= V, or CG_BF16X2 (split hi | lo
+ * halves of ldd / 2 >= V columns, as cg_cross_entropy writes them); the pad columns [V, ldd) -- of
+ * each half -- are zero.  Row r has the class y[r] (device int64) and the weight w[r] (device fp32;
+ * w NULL = 1):
+ *   CG_ATTR_LOGPROB: d[r][c] = w (delta_{c,y} - softmax(z_r)_c), the gradient of the objective
+ *     sum_r w_r log p(y_r | row r) -- a sum, not a mean, so a row's seed does not depend on the
+ *     other rows;
+ *   CG_ATTR_LOGIT:   d[r][c] = w delta_{c,y} (logits is not read and may be NULL).
+ * A row with y < 0, y >= V or w == 0 is all zero.  The softmax is evaluated in fp64 from the fp32
+ * logits and every stored value is the single rounding of the fp64 one.  One wave per row, any V.
+ * rows == 0: CG_OK, nothing touched.  CG_EINVAL: NULL y / d, LOGPROB without logits, ldl < V, a
+ * short ldd, another mode; CG_EUNSUPPORTED: another d_dtype. */
+enum { CG_ATTR_LOGPROB = 0, CG_ATTR_LOGIT = 1 };
+int cg_attr_seed(const float* logits, long long ldl, const int64_t* y, const float* w, int rows, int V,
+                 int mode, int d_dtype, void* d, long long ldd, void* stream);
+/* cg_attr_reduce: the per-token reductions of an input gradient g fp32 [rows][ldg] over its d
+ * columns, each output optional (NULL = not wanted), fp32 [rows]:
+ *   gxt[r]   = sum_k g[r][k] tok_emb[idx[r]][k]  (tok_emb fp32 [V][ld_e]; 0 where idx[r] is outside
+ *              [0, V)) -- what analyze_saliency.py :79-81 computes: its hook sits on tok_emb, so the
+ *              position embedding is not part of the activation;
+ *   gxi[r]   = sum_k g[r][k] x0[r][k]            (x0 fp32 [rows][ldx]: the embedding output, tok + pos);
+ *   gnorm[r] = sqrt(sum_k g[r][k]^2).
+ * One wave per row; lane l adds elements 4 (l + 64 j) .. + 3, j ascending, as one FMA chain per
+ * output and a fixed butterfly follows (16-byte loads when d % 4 == 0 and every operand's rows are
+ * 16-byte aligned, element loads otherwise -- the same order either way): a row's values are bitwise
+ * independent of the other rows and of the row count.  rows == 0: CG_OK, nothing touched.
+ * CG_EINVAL (before any launch): NULL g / idx, gxt without tok_emb, gxi without x0, a stride < d. */
+int cg_attr_reduce(const float* g, long long ldg, const int64_t* idx, const float* tok_emb, long long ld_e,
+                   int V, const float* x0, long long ldx, int rows, int d, float* gxt, float* gxi,
+                   float* gnorm, void* stream);
+/* cg_model_input_grad: d(objective)/d(embedding output) of the last forward, which must have been
+ * an eval forward (training == 0), and its per-token reductions.
+ *   seed: y != NULL -- cg_attr_seed(mode, y [B*T], w [B*T] or NULL) over the forward's logits: the
+ *     objective is sum_r w_r log p(y_r) (or the weighted logits).  y == NULL -- the dlogits the
+ *     forward's fused cross-entropy left, i.e. the model's own mean loss with its label smoothing
+ *     and class weights (the loss analyze_saliency.py :57-70 differentiates); the forward must have
+ *     had targets, and no seeded call may have run since (a seeded call overwrites that buffer).
+ *   outputs, all optional: gxt / gxi / gnorm fp32 [B*T] (cg_attr_reduce of the gradient with the
+ *     forward's idx, the fp32 master tok_emb and hidden state 0), dx0 fp32 [B*T][ld_dx0 >= n_embd]
+ *     (the gradient itself).
+ * It runs the dX products, LayerNorm and attention backward kernels of cg_model_backward with the
+ * same operands (window, SEP segments, GQA, RoPE), block L-1 down to 0, and none of the parameter
+ * gradient work: no dW product, no bias column sum, no LayerNorm parameter reduction, no embedding
+ * scatter.  The aux heads contribute nothing (the seed is on the next-codon head).  m->grads may be
+ * NULL and is never written; head_dw_pending, reduce_pending and dw_done_layer are left as they
+ * are; the workspace of cg_model_workspace_bytes suffices.  The forward's activations and logits
+ * stay intact, so it can be called again with another seed.
+ * CG_EINVAL: NULL m / a, no forward yet, a training forward, y == NULL after a forward without
+ * targets, an unknown mode, dx0 with ld_dx0 < n_embd. */
+typedef struct {
+  const int64_t* y;  /* device [B*T] or NULL */
+  const float* w;    /* device [B*T] or NULL (= 1) */
+  int mode;          /* CG_ATTR_LOGPROB / CG_ATTR_LOGIT (read with y) */
+  float* gxt; float* gxi; float* gnorm;
+  float* dx0; long long ld_dx0;
+} cg_attr_desc;
+int cg_model_input_grad(cg_model* m, const cg_attr_desc* a, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -793,7 +857,7 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
 /* sizeof the named ABI struct ("cg_gemm_desc", "cg_dw_product", "cg_dw_group", "cg_reduce_job",
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
- * "cg_score_desc", "cg_sample_plan", "cg_offset_prior"), 0 for
+ * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -813,7 +877,8 @@ size_t cg_struct_bytes(const char* name);
  * sets and drawn-token log-probabilities -- cg_sample_step_plan with cg_sample_plan, CG_GEN_PLAN_END.
  * ABI 0.6, additions: multi-offset priors in batched generation -- cg_xf_hist_bytes,
  * cg_model_prefill_hist, cg_model_decode_ragged_hist, cg_offset_prior_workspace and
- * cg_offset_prior_add with cg_offset_prior. */
+ * cg_offset_prior_add with cg_offset_prior.  ABI 0.6, additions: input attribution -- cg_attr_seed,
+ * cg_attr_reduce and cg_model_input_grad with cg_attr_desc. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

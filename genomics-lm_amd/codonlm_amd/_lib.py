@@ -187,6 +187,16 @@ class AttrDesc(C.Structure):
                 ("dx0", vp), ("ld_dx0", i64)]
 
 
+KMEANS_CHUNK = 4096  # CG_KMEANS_CHUNK: the rows one fp32 partial of cg_kmeans_step's statistics covers
+
+
+class KMeansDesc(C.Structure):
+    """cg_kmeans_desc: dist2, sums (with counts) and inertia are optional (None = not wanted)"""
+    _fields_ = [("x", vp), ("ldx", i64), ("n", i64), ("d", i32), ("centers", vp), ("ldc", i64), ("k", i32),
+                ("labels", vp), ("dist2", vp), ("sums", vp), ("counts", vp), ("inertia", vp),
+                ("workspace", vp), ("ws_bytes", sz)]
+
+
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {
     "cg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -279,6 +289,10 @@ SIGNATURES = {
     "cg_attr_seed": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
     "cg_attr_reduce": (i32, [vp, i64, vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     "cg_model_input_grad": (i32, [C.POINTER(Model), C.POINTER(AttrDesc), vp]),
+    "cg_window_keep": (i32, [vp, i32, i32, i32, i32, C.POINTER(u32), vp, vp]),
+    "cg_window_pool": (i32, [i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, i64, i64, vp]),
+    "cg_kmeans_workspace": (sz, [i64, i32, i32]),
+    "cg_kmeans_step": (i32, [C.POINTER(KMeansDesc), vp]),
     "cg_model_hidden": (vp, [C.POINTER(Model), i32, C.POINTER(i32), C.POINTER(i64)]),
     "cg_model_attn_probs": (i32, [C.POINTER(Model), i32, vp, vp]),
     "cg_probe_enable": (i32, [i32]),

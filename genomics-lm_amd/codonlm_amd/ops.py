@@ -785,3 +785,94 @@ def gemm_dw_grouped(products, *, tile_m=0, ksplit=1, max_wg=0, workspace=None):
         g.workspace, g.ws_bytes = ws.data_ptr(), ws.numel() * 4
     L.check(L.lib.cg_gemm_dw_grouped(C.byref(g), L.stream_ptr(products[0][0].device)), "cg_gemm_dw_grouped")
     return ws
+
+
+def _id_mask(ids, what):
+    words = [0] * 8
+    for t in ids:
+        t = int(t)
+        if not 0 <= t < 256:
+            raise ValueError(f"{what} must be in [0, 256)")
+        words[t >> 5] |= 1 << (t & 31)
+    return (C.c_uint32 * 8)(*words)
+
+
+def window_count(T: int, window: int, stride: int) -> int:
+    """Sliding windows of one sequence of T positions (motif_extractor.py:13-17)."""
+    return (T - window) // stride + 1 if T >= window else 0
+
+
+def window_keep(idx, window, stride, exclude_ids=()):
+    """int32 (B, nwin): 1 where no token of window j of idx (B, T) is in exclude_ids
+    (motif_extractor.py:71-77)."""
+    L.require_device(idx, "window_keep")
+    idx = idx.to(torch.int64).contiguous()
+    B, T = idx.shape
+    if window < 1 or stride < 1:
+        raise ValueError("window and stride must be at least 1")
+    keep = torch.empty(B, window_count(T, window, stride), dtype=torch.int32, device=idx.device)
+    L.check(L.lib.cg_window_keep(idx.data_ptr(), B, T, int(window), int(stride), _id_mask(exclude_ids, "exclude ids"),
+                                 keep.data_ptr(), L.stream_ptr(idx.device)), "cg_window_keep")
+    return keep
+
+
+def window_pool(hidden, window, stride, dst_row, out):
+    """Mean of hidden (B, T, d; fp32 or bf16, read in place) over every sliding window, written to
+    row dst_row[b, j] of out (fp32, rows >= d wide); a row index outside out is skipped
+    (motif_extractor.py:80-83).  Returns out."""
+    for t in (hidden, dst_row, out):
+        L.require_device(t, "window_pool")
+    B, T, d = hidden.shape
+    if hidden.stride(2) != 1 or hidden.stride(0) != T * hidden.stride(1):
+        hidden = hidden.contiguous()
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != d or (out.shape[0] > 1 and out.stride(1) != 1):
+        raise ValueError("window_pool: out must be fp32 (rows, d) with unit column stride")
+    nwin = window_count(T, window, stride)
+    if dst_row.dtype != torch.int32 or dst_row.numel() != B * nwin or not dst_row.is_contiguous():
+        raise ValueError("window_pool: dst_row must be a contiguous int32 (B, nwin)")
+    L.check(L.lib.cg_window_pool(_dt(hidden), hidden.data_ptr(), hidden.stride(1), B, T, d, int(window), int(stride),
+                                 dst_row.data_ptr(), out.data_ptr(), out.stride(0), out.shape[0],
+                                 L.stream_ptr(hidden.device)), "cg_window_pool")
+    return out
+
+
+class KMeansStep:
+    """Outputs of kmeans_step; an output that was not asked for is None."""
+    __slots__ = ("labels", "dist2", "sums", "counts", "inertia")
+
+    def __init__(self, labels=None, dist2=None, sums=None, counts=None, inertia=None):
+        self.labels, self.dist2, self.sums, self.counts, self.inertia = labels, dist2, sums, counts, inertia
+
+
+def kmeans_step(x, centers, *, want_dist2=True, want_stats=True, want_inertia=True, workspace=None):
+    """One E-step of Lloyd's algorithm with the M-step's statistics (cg_kmeans_step): labels int32
+    (n), dist2 fp32 (n), sums fp64 (k, d), counts int64 (k), inertia fp64 scalar tensor.  x fp32
+    (n, d) and centers fp32 (k, d) may have padded rows.  workspace: a uint8 buffer to reuse."""
+    for t in (x, centers):
+        L.require_device(t, "kmeans_step")
+        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError("kmeans_step: fp32 matrices with unit column stride")
+    n, d = x.shape
+    k = centers.shape[0]
+    if centers.shape[1] != d:
+        raise ValueError("kmeans_step: points and centres differ in width")
+    dev = x.device
+    r = KMeansStep(labels=torch.empty(n, dtype=torch.int32, device=dev))
+    if want_dist2:
+        r.dist2 = torch.empty(n, dtype=torch.float32, device=dev)
+    if want_stats:
+        r.sums = torch.zeros(k, d, dtype=torch.float64, device=dev)
+        r.counts = torch.zeros(k, dtype=torch.int64, device=dev)
+    if want_inertia:
+        r.inertia = torch.zeros((), dtype=torch.float64, device=dev)
+    need = int(L.lib.cg_kmeans_workspace(n, d, k))
+    ws = workspace
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    p = L.KMeansDesc()
+    p.x, p.ldx, p.n, p.d = x.data_ptr(), x.stride(0) if n > 1 else max(d, x.stride(0)), n, d
+    p.centers, p.ldc, p.k = centers.data_ptr(), centers.stride(0) if k > 1 else max(d, centers.stride(0)), k
+    p.labels, p.dist2, p.sums, p.counts, p.inertia = _p(r.labels), _p(r.dist2), _p(r.sums), _p(r.counts), _p(r.inertia)
+    p.workspace, p.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    L.check(L.lib.cg_kmeans_step(C.byref(p), L.stream_ptr(dev)), "cg_kmeans_step")
+    return r

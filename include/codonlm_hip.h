@@ -821,6 +821,64 @@ typedef struct {
 } cg_attr_desc;
 int cg_model_input_grad(cg_model* m, const cg_attr_desc* a, void* stream);
 
+/* Motif mining (ABI 0.6 addition): sliding-window pooling of hidden states and a deterministic
+ * k-means step.  Replaces the per-window Python loop of the reference's src/eval/motif_extractor.py
+ * and the host sklearn.KMeans of src/eval/motif_clusterer.py (scripts/mine_motifs.py).
+ * Windows: nwin = T >= window ? (T - window) / stride + 1 : 0 per sequence, window j of sequence b
+ * covers positions j*stride .. j*stride + window - 1.
+ *
+ * cg_window_keep (motif_extractor.py:71-77): keep[b*nwin + j] = 1 when no token of the window is in
+ * exclude_mask (host, 8 x 32-bit words = ids 0..255, the convention of cg_pool_hidden's
+ * content_mask), else 0.  An id outside 0..255 is never excluded.  idx device int64 [B][T].
+ * B == 0 or nwin == 0: CG_OK, nothing touched.  CG_EINVAL: NULL idx / exclude_mask / keep, B or T
+ * negative, window < 1, stride < 1. */
+int cg_window_keep(const int64_t* idx, int B, int T, int window, int stride, const uint32_t* exclude_mask,
+                   int32_t* keep, void* stream);
+/* cg_window_pool (motif_extractor.py:80-83): h is a hidden-state buffer as cg_model_hidden returns it
+ * ([B*T rows][ldh], CG_F32 or CG_BF16).  For window (b, j) with r = dst_row[b*nwin + j] (device
+ * int32): r < 0 or r >= out_rows writes nothing; otherwise out[r][c] (fp32 [out_rows][ldo]), c < d,
+ * is the sum over t = j*stride .. j*stride + window - 1 of h[b*T + t][c], taken in fp32 in ascending
+ * t, divided by window.  The pad columns [d, ldh) and [d, ldo) are neither read nor written.  The
+ * caller makes dst_row from cg_window_keep's flags with a prefix sum, so the kept windows of many
+ * forwards land back to back in one [N][d] matrix in (sequence, window start) order.
+ * B == 0, d == 0 or nwin == 0: CG_OK, nothing touched.  CG_EINVAL: NULL h / dst_row / out, ldh < d,
+ * ldo < d, window < 1, stride < 1, a negative size; CG_EUNSUPPORTED: another dtype. */
+int cg_window_pool(int dtype, const void* h, long long ldh, int B, int T, int d, int window, int stride,
+                   const int32_t* dst_row, float* out, long long ldo, long long out_rows, void* stream);
+/* cg_kmeans_step: the E-step of Lloyd's algorithm and the sufficient statistics of its M-step for
+ * fp32 points x [n][ldx] (d used columns) and centres [k][ldc] (KMeans.fit of motif_clusterer.py:37-48).
+ *   labels[i] (required) = the nearest centre in squared Euclidean distance, ranked by
+ *     |c|^2 - 2 x.c with the products on the exact-fp32 MFMA; an exact tie of that score (two
+ *     identical centres among them) goes to the lowest index.
+ *   dist2[i] (optional) = sum_j (x[i][j] - c[label][j])^2 formed directly in fp32 (not from the
+ *     ranking score): lane l of one wave adds columns l, l + 64, ... in order, a fixed butterfly follows.
+ *   sums (optional, fp64 [k][d] contiguous) and counts (long long [k], required with sums): the sum and
+ *     the number of the points labelled c; a cluster without points gets 0 and a zero row.  Rows are
+ *     taken in chunks of CG_KMEANS_CHUNK: a chunk is cut into 1..16 equal row ranges (a number fixed by
+ *     k), a range's values of a column are added in row order into an fp32 word of shared memory that
+ *     one thread alone touches, the ranges' words are added in range order (fp32: at most
+ *     CG_KMEANS_CHUNK additions per partial) and the chunks' partials in chunk order in fp64.
+ *   inertia (optional, device fp64) = the sum of dist2, per-workgroup fp64 partials added in a fixed
+ *     order.
+ * No floating-point atomics anywhere; every sum is taken in an order fixed by (n, d, k): the same
+ * inputs give the same bits.  The pad columns of x and centres are never read.
+ * n == 0: CG_OK, nothing touched.  CG_EUNSUPPORTED: k outside 1..256 or d outside 1..1024.
+ * CG_EINVAL: a NULL desc / x / centers / labels / workspace, n < 0, ldx < d, ldc < d, sums without
+ * counts, ws_bytes below cg_kmeans_workspace(n, d, k) (workspace 16-byte aligned). */
+#define CG_KMEANS_CHUNK 4096
+typedef struct {
+  const float* x; long long ldx; long long n; int d;
+  const float* centers; long long ldc; int k;
+  int32_t* labels;
+  float* dist2;
+  double* sums;
+  long long* counts;
+  double* inertia;
+  void* workspace; size_t ws_bytes;
+} cg_kmeans_desc;
+size_t cg_kmeans_workspace(long long n, int d, int k);
+int cg_kmeans_step(const cg_kmeans_desc* k, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -857,7 +915,7 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
 /* sizeof the named ABI struct ("cg_gemm_desc", "cg_dw_product", "cg_dw_group", "cg_reduce_job",
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
- * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc"), 0 for
+ * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc", "cg_kmeans_desc"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -878,7 +936,8 @@ size_t cg_struct_bytes(const char* name);
  * ABI 0.6, additions: multi-offset priors in batched generation -- cg_xf_hist_bytes,
  * cg_model_prefill_hist, cg_model_decode_ragged_hist, cg_offset_prior_workspace and
  * cg_offset_prior_add with cg_offset_prior.  ABI 0.6, additions: input attribution -- cg_attr_seed,
- * cg_attr_reduce and cg_model_input_grad with cg_attr_desc. */
+ * cg_attr_reduce and cg_model_input_grad with cg_attr_desc.  ABI 0.6, additions: motif mining --
+ * cg_window_keep, cg_window_pool, cg_kmeans_step with cg_kmeans_desc, and cg_kmeans_workspace. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

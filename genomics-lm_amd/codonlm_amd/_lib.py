@@ -131,7 +131,9 @@ class Model(C.Structure):
                 ("ld_d_term", i64),
                 ("d_offset_logits", vp * 8), ("dw_done_layer", i32),
                 ("head_dw_off", i64), ("head_dw_alpha", f32), ("head_dw_accumulate", i32), ("head_dw_pending", i32),
-                ("reduce_pending", ReduceBatch)]
+                ("reduce_pending", ReduceBatch),
+                ("term_fused", i32), ("term_labels", vp), ("term_class_w", vp), ("term_scale", f32),
+                ("term_scale_dev", vp)]
 
 
 # cg_sample_step: token classes, sequence flags, parameters and the per-sequence state
@@ -195,6 +197,18 @@ class KMeansDesc(C.Structure):
     _fields_ = [("x", vp), ("ldx", i64), ("n", i64), ("d", i32), ("centers", vp), ("ldc", i64), ("k", i32),
                 ("labels", vp), ("dist2", vp), ("sums", vp), ("counts", vp), ("inertia", vp),
                 ("workspace", vp), ("ws_bytes", sz)]
+
+
+TERM_CE_MAX_CLASSES = 16  # cg_term_ce_fwd / _bwd: more classes are CG_EUNSUPPORTED
+
+
+class TermCeDesc(C.Structure):
+    """cg_term_ce_desc: loss, sums, dW, db and dx are optional (None = not wanted)"""
+    _fields_ = [("x_dtype", i32), ("x", vp), ("ldx", i64), ("rows", i64), ("d", i32), ("C", i32),
+                ("W", vp), ("ldw", i64), ("bias", vp), ("labels", vp), ("ignore_index", i32), ("class_w", vp),
+                ("loss", vp), ("sums", vp), ("scale", f32), ("scale_dev", vp),
+                ("dW", vp), ("lddw", i64), ("acc_dW", i32), ("db", vp), ("acc_db", i32),
+                ("dx", vp), ("lddx", i64), ("acc_dx", i32), ("workspace", vp), ("ws_bytes", sz)]
 
 
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
@@ -293,6 +307,12 @@ SIGNATURES = {
     "cg_window_pool": (i32, [i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, i64, i64, vp]),
     "cg_kmeans_workspace": (sz, [i64, i32, i32]),
     "cg_kmeans_step": (i32, [C.POINTER(KMeansDesc), vp]),
+    "cg_term_ce_workspace": (sz, [i64, i32, i32]),
+    "cg_term_ce_fwd": (i32, [C.POINTER(TermCeDesc), vp]),
+    "cg_term_ce_bwd": (i32, [C.POINTER(TermCeDesc), vp]),
+    "cg_model_forward_trunk": (i32, [C.POINTER(Model), vp, i32, i32, i32, u32, i32, vp]),
+    "cg_model_term_loss": (i32, [C.POINTER(Model), vp, vp, vp, vp]),
+    "cg_model_backward_heads": (i32, [C.POINTER(Model), i32, vp]),
     "cg_model_hidden": (vp, [C.POINTER(Model), i32, C.POINTER(i32), C.POINTER(i64)]),
     "cg_model_attn_probs": (i32, [C.POINTER(Model), i32, vp, vp]),
     "cg_probe_enable": (i32, [i32]),

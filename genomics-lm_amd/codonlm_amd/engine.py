@@ -162,8 +162,13 @@ class Engine:
     # -- compute ----------------------------------------------------------------------
     def forward(self, idx: torch.Tensor, targets: torch.Tensor | None, *, training: bool, seed: int = 0,
                 window: int | None = None, logits: torch.Tensor | None = None,
-                loss: torch.Tensor | None = None):
+                loss: torch.Tensor | None = None, head: bool = True):
+        """``head=False``: the trunk alone (cg_model_forward_trunk) -- through ln_f, no head product,
+        no logits, no loss; returns (None, None).  The aux heads, term_loss, hidden and the backward
+        work after it."""
         L.require_device(idx, "TinyGPT.forward")
+        if not head and targets is not None:
+            raise ValueError("head=False computes no next-codon loss: targets must be None")
         if idx.dim() != 2:
             raise ValueError("idx must be (B, T)")
         B, T = idx.shape
@@ -179,6 +184,14 @@ class Engine:
                 raise ValueError("targets must have the same shape as idx")
         self._ensure_workspace(B, T)
         self.sync_shadow()
+        self._term_keep = None
+        if not head:
+            self._idx, self._targets = idx, None
+            self._dlogits_seeded = False
+            L.check(L.lib.cg_model_forward_trunk(C.byref(self.model), idx.data_ptr(), B, T, int(bool(training)),
+                                                 int(seed) & 0xFFFFFFFF, int(window) if window is not None else 0,
+                                                 L.stream_ptr(dev)), "cg_model_forward_trunk")
+            return None, None
         if logits is None:
             logits = torch.empty(B, T, self.cfg.vocab_size, dtype=torch.float32, device=dev)
         if targets is not None and loss is None:
@@ -213,14 +226,58 @@ class Engine:
             wsb = self._score_ws = ops.score_workspace(B * T, buf.device)
         return ops.score_rows(self.score_logits.view(B * T, V), targets, T=T, workspace=wsb, **kw)
 
-    def aux_forward(self):
+    def term_loss(self, labels: torch.Tensor, class_weights: torch.Tensor | None = None) -> torch.Tensor:
+        """termination_aux_loss (objectives.py:94-105) of the last forward's ln_f output through the
+        fused kernel (cg_model_term_loss): a 0-d fp32 device tensor, no logits.  labels int64 with
+        one entry per position (-100 = ignored), class_weights fp32 (n_classes) or None.  The
+        next backward takes the head's gradients from the fused path, scaled by set_term_grad."""
+        m = self.model
+        dev = self.flat.device
+        if not self.cfg.termination_aux:
+            raise ValueError("term_loss: the model has no termination head")
+        if m.B <= 0 or labels.numel() != m.B * m.T:
+            raise ValueError("term_loss: labels need one entry per position of the last forward")
+        L.require_device(labels, "term_loss")
+        lab = labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        cw = None
+        if class_weights is not None:
+            cw = class_weights.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+            if cw.numel() != self.cfg.termination_n_classes:
+                raise ValueError("term_loss: class_weights need one entry per termination class")
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        self._term_keep = (lab, cw)  # read again by the backward
+        L.check(L.lib.cg_model_term_loss(C.byref(m), lab.data_ptr(), cw.data_ptr() if cw is not None else None,
+                                         loss.data_ptr(), L.stream_ptr(dev)), "cg_model_term_loss")
+        return loss
+
+    def set_term_grad(self, scale: float, scale_dev=None):
+        """d(objective)/d(termination loss) of the fused path: a host float times an optional
+        one-element device tensor (read in the kernel, no host sync), as set_head_grads' scale."""
+        m = self.model
+        m.term_scale = float(scale)
+        m.term_scale_dev = None
+        self._term_scale_keep = None
+        if scale_dev is not None:
+            sd = scale_dev.detach().reshape(1).to(torch.float32).contiguous()
+            self._term_scale_keep = sd
+            m.term_scale_dev = sd.data_ptr()
+
+    def backward_heads(self, accumulate: bool = False):
+        """cg_model_backward_heads: the aux parameters' gradients alone (a frozen backbone)."""
+        L.check(L.lib.cg_model_backward_heads(C.byref(self.model), int(bool(accumulate)),
+                                              L.stream_ptr(self.flat.device)), "cg_model_backward_heads")
+
+    def aux_forward(self, term: bool = True):
         """Aux heads of the last forward (model_tiny_gpt.py:329-337): termination logits
-        fp32 (M, n_classes) or None, and [offset logits fp32 (M, V)] in offset order."""
+        fp32 (M, n_classes) or None, and [offset logits fp32 (M, V)] in offset order.  ``term=False``
+        (after term_loss only): the offset heads alone, no termination logits."""
         cfg = self.cfg
         dev = self.flat.device
         M = self.model.B * self.model.T
-        term = None
-        if cfg.termination_aux:
+        want_term, term = term, None
+        if not want_term and not self.model.term_fused:
+            raise ValueError("aux_forward(term=False) needs term_loss first")
+        if cfg.termination_aux and want_term:
             term = torch.empty(M, cfg.termination_n_classes, dtype=torch.float32, device=dev)
         # rows padded to a multiple of 16 columns (the GEMM then takes the vector tiles); the
         # callers see [:, :V] views

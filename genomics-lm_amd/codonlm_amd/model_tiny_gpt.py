@@ -177,6 +177,8 @@ class _AuxEngineBackward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, anchor, has_loss, has_term, *outs):
+        # has_term == "fused": the termination slot holds the fused termination LOSS (a scalar), and
+        # its incoming gradient becomes the kernel's device-side scale
         ctx.model, ctx.has_loss, ctx.has_term = model, has_loss, has_term
         ctx.set_materialize_grads(False)  # unused heads arrive as None (their grads are zeroed)
         if has_loss:
@@ -191,7 +193,10 @@ class _AuxEngineBackward(torch.autograd.Function):
             g_loss, i = grads[0], 1
         if ctx.has_term:
             g_term, i = grads[i], i + 1
-        ctx.model._native_backward(g_loss, d_term=g_term, d_offsets=list(grads[i:]))
+        if ctx.has_term == "fused":
+            ctx.model._native_backward(g_loss, d_offsets=list(grads[i:]), term_fused=True, g_term_loss=g_term)
+        else:
+            ctx.model._native_backward(g_loss, d_term=g_term, d_offsets=list(grads[i:]))
         return (None, None, None, None) + (None,) * len(grads)
 
 
@@ -306,10 +311,12 @@ class TinyGPT(nn.Module):
             p = getattr(mod, attr)
             p.data = self._view(self._flat, spec)
             g = self._view(self._flat_grad, spec)
-            p.grad = g
+            p.grad = g if p.requires_grad else None
             pairs.append((p, g))
         # (parameter, its view of the flat grad buffer): re-attached by _bind_grad_views
         self._grad_pairs = pairs
+        # the aux-head parameters (the reference's freeze_backbone name match, loop.py:656-667)
+        self._aux_param = [n.startswith(("termination_head", "offset_projs")) for n in self._specs]
 
     @torch.no_grad()
     def _reference_init(self):
@@ -405,22 +412,54 @@ class TinyGPT(nn.Module):
         # replaced or set to None are re-attached -- re-creating and re-assigning every view took
         # milliseconds of host time per step and left the GPU idle between optimizer step and
         # the next forward
+        # a frozen parameter (requires_grad False) keeps grad None, as under torch's autograd
         for p, g in self._grad_pairs:
-            if p.grad is not g:
-                p.grad = g
+            if p.requires_grad:
+                if p.grad is not g:
+                    p.grad = g
+            elif p.grad is not None:
+                p.grad = None
 
-    def _native_backward(self, gout, d_term=None, d_offsets=None):
+    def _frozen_backbone(self):
+        """(heads_only, probe): heads_only when every parameter outside termination_head /
+        offset_projs is frozen and an aux parameter trains; probe = the first trainable parameter
+        (its grad set to None by an optimizer marks a fresh accumulation group)."""
+        probe, backbone_trains = None, False
+        for (p, _), aux in zip(self._grad_pairs, self._aux_param):
+            if p.requires_grad:
+                if probe is None:
+                    probe = p
+                if not aux:
+                    backbone_trains = True
+                    break
+        if probe is None:
+            raise RuntimeError("TinyGPT backward: no parameter requires a gradient")
+        return not backbone_trains, probe
+
+    def _native_backward(self, gout, d_term=None, d_offsets=None, term_fused=False, g_term_loss=None):
         """Native backward of the last forward: ``gout`` = d(objective)/d(loss) (None when the
-        next-codon loss is unused), ``d_term`` / ``d_offsets`` = gradients of the aux logits."""
+        next-codon loss is unused), ``d_term`` / ``d_offsets`` = gradients of the aux logits;
+        ``term_fused``: the termination loss came from the fused kernel and ``g_term_loss`` is its
+        incoming gradient (None = unused).  With a frozen backbone only the aux heads' gradients
+        are computed (cg_model_backward_heads)."""
+        heads_only, probe = self._frozen_backbone()
         # an optimizer that set grads to None means "fresh group"
-        if self.tok_emb.weight.grad is None:
+        if probe.grad is None:
             self._grads_fresh = True
         eng = self.engine
         # d(objective)/d(loss) stays on the device: the engine scales the head gradient in-kernel
         eng.set_head_grads(0.0 if gout is None else 1.0, d_term, d_offsets,
                            scale_dev=None if gout is None else gout)
+        if term_fused:
+            eng.set_term_grad(0.0 if g_term_loss is None else 1.0, g_term_loss)
         hook, self._bucket_hook = self._bucket_hook, None
-        eng.backward(accumulate=not self._grads_fresh, bucket_hook=hook)
+        if heads_only:
+            if hook:
+                raise RuntimeError("a frozen-backbone backward has no gradient buckets: all-reduce the aux "
+                                   "parameters' range after the group instead of passing a bucket hook")
+            eng.backward_heads(accumulate=not self._grads_fresh)
+        else:
+            eng.backward(accumulate=not self._grads_fresh, bucket_hook=hook)
         self._grads_fresh = False
         self._bind_grad_views()
 
@@ -470,42 +509,72 @@ class TinyGPT(nn.Module):
         return mix_seed_rank(self._dropout_seed, self._seed_rank)
 
     def forward(self, idx, targets=None, return_aux: bool = False, shape_embeddings=None,
-                attention_window: int | None = None):
+                attention_window: int | None = None, termination_labels=None, termination_class_weights=None,
+                head: bool = True):
+        """Beyond the reference's arguments: ``termination_labels`` (B, T) int64 (-100 = ignored; needs
+        return_aux and a termination head) makes aux carry ``termination_loss`` -- termination_aux_loss
+        of those labels with ``termination_class_weights``, a differentiable scalar from the fused
+        kernel -- instead of ``termination_logits``.  ``head=False`` skips the next-codon head:
+        logits is None and targets must be None; together with ``termination_labels`` (a replay
+        batch) the offset heads, which end in a head product too, are not evaluated either and aux
+        holds ``termination_loss`` alone."""
         if shape_embeddings is not None:
             raise ValueError("shape guidance is not supported on the MI355X path")
+        if not head and targets is not None:
+            raise ValueError("head=False computes no next-codon loss: targets must be None")
+        if termination_labels is not None and not (return_aux and self.termination_aux):
+            raise ValueError("termination_labels need return_aux=True and a model with termination_aux")
+        if termination_labels is None and termination_class_weights is not None:
+            raise ValueError("termination_class_weights need termination_labels")
         if return_aux and (self.termination_aux or self.multi_offset_targets):
-            return self._forward_aux(idx, targets, attention_window)
+            return self._forward_aux(idx, targets, attention_window, termination_labels, termination_class_weights,
+                                     head)
         eng = self.engine
         training = self.training and self.dropout_p > 0
         seed = self.next_dropout_seed() if training else 0
-        logits, loss = eng.forward(idx, targets, training=training, seed=seed, window=attention_window)
+        logits, loss = eng.forward(idx, targets, training=training, seed=seed, window=attention_window, head=head)
         self._capture_attention()
         if loss is not None and self.training and torch.is_grad_enabled():
-            loss = _EngineBackward.apply(loss, self.tok_emb.weight, self)
+            loss = _EngineBackward.apply(loss, self._frozen_backbone()[1], self)
         if return_aux:
             return logits, loss, {}
         return logits, loss
 
-    def _forward_aux(self, idx, targets, attention_window):
+    def _forward_aux(self, idx, targets, attention_window, term_labels=None, term_class_weights=None, head=True):
         """forward(..., return_aux=True) with aux heads: (logits, loss, {termination_logits,
-        offset_logits: {k: (B,T,V)}}) as model_tiny_gpt.py:326-351, all on the native engine."""
+        offset_logits: {k: (B,T,V)}}) as model_tiny_gpt.py:326-351, all on the native engine.
+        With term_labels the termination head's slot holds the fused termination loss instead."""
         eng = self.engine
         training = self.training and self.dropout_p > 0
         seed = self.next_dropout_seed() if training else 0
-        logits, loss = eng.forward(idx, targets, training=training, seed=seed, window=attention_window)
-        term, offs = eng.aux_forward()
+        logits, loss = eng.forward(idx, targets, training=training, seed=seed, window=attention_window, head=head)
         B, T = idx.shape
-        outs = ([loss] if loss is not None else []) + ([term.view(B, T, -1)] if term is not None else []) + \
+        fused = term_labels is not None
+        if fused:
+            if tuple(term_labels.shape) != (B, T):
+                raise ValueError("termination_labels must have the shape of idx")
+            term = eng.term_loss(term_labels, term_class_weights)
+            # head=False: no product with the head weight at all -- the offset heads end in one, and
+            # a replay batch has no loss on them
+            offs = eng.aux_forward(term=False)[1] if self.multi_offset_targets and head else []
+        else:
+            term, offs = eng.aux_forward()
+            if term is not None:
+                term = term.view(B, T, -1)
+        outs = ([loss] if loss is not None else []) + ([term] if term is not None else []) + \
             [o.view(B, T, -1) for o in offs]
         if self.training and torch.is_grad_enabled():
-            outs = list(_AuxEngineBackward.apply(self, self.tok_emb.weight, loss is not None, term is not None,
-                                                 *outs))
+            # (the anchor is the first trainable parameter: tok_emb.weight unless it is frozen)
+            outs = list(_AuxEngineBackward.apply(self, self._frozen_backbone()[1], loss is not None,
+                                                 "fused" if fused else term is not None, *outs))
         if loss is not None:
             loss = outs.pop(0)
         aux = {}
-        if term is not None:
+        if fused:
+            aux["termination_loss"] = outs.pop(0)
+        elif term is not None:
             aux["termination_logits"] = outs.pop(0)
-        if self.multi_offset_targets:
+        if self.multi_offset_targets and offs:
             aux["offset_logits"] = {k: outs[i] for i, k in enumerate(self.multi_offset_targets)}
         return logits, loss, aux
 

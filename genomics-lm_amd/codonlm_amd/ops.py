@@ -876,3 +876,99 @@ def kmeans_step(x, centers, *, want_dist2=True, want_stats=True, want_inertia=Tr
     p.workspace, p.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     L.check(L.lib.cg_kmeans_step(C.byref(p), L.stream_ptr(dev)), "cg_kmeans_step")
     return r
+
+
+class TermCE:
+    """State of term_ce_fwd: ``loss`` (0-d fp32) and ``sums`` (2,) = (sum w nll, sum w), and the
+    operands and workspace term_ce_bwd reads again."""
+    __slots__ = ("loss", "sums", "x", "W", "bias", "labels", "class_w", "ignore_index", "workspace")
+
+
+def _rows2d(t, what, dtypes):
+    if t.dtype not in dtypes or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: a 2-D {' / '.join(str(d) for d in dtypes)} matrix with unit column stride")
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+
+
+def _term_ce_desc(st: TermCE):
+    x, W = st.x, st.W
+    p = L.TermCeDesc()
+    p.x_dtype, p.x, p.ldx = _dt(x), x.data_ptr(), _rows2d(x, "term_ce: x", (torch.float32, torch.bfloat16))
+    p.rows, p.d, p.C = x.shape[0], x.shape[1], W.shape[0]
+    p.W, p.ldw = W.data_ptr(), _rows2d(W, "term_ce: W", (torch.float32,))
+    p.bias, p.labels, p.ignore_index, p.class_w = st.bias.data_ptr(), st.labels.data_ptr(), st.ignore_index, _p(st.class_w)
+    p.workspace, p.ws_bytes = st.workspace.data_ptr(), st.workspace.numel() * st.workspace.element_size()
+    return p
+
+
+def term_ce_fwd(x, W, bias, labels, *, class_w=None, ignore_index=-100, workspace=None) -> TermCE:
+    """Fused termination-head loss (cg_term_ce_fwd): the class-weighted cross-entropy of
+    x W^T + bias against labels over the labelled rows, without materialising the logits.
+    x (rows, d) fp32 or bf16, W fp32 (C, d), C <= 16, bias fp32 (C), labels int64 (rows), class_w
+    fp32 (C) or None; x and W may have padded rows.  A label equal to ignore_index or outside
+    [0, C) is ignored.  No labelled row: the loss is NaN.  Returns the state term_ce_bwd takes."""
+    for t in (x, W, bias, labels) + (() if class_w is None else (class_w,)):
+        L.require_device(t, "term_ce_fwd")
+    if x.dim() != 2 or W.dim() != 2:
+        raise ValueError("term_ce_fwd: x (rows, d) and W (C, d)")
+    rows, d = x.shape
+    nc = W.shape[0]
+    if W.shape[1] != d or bias.numel() != nc or labels.numel() != rows or (class_w is not None and class_w.numel() != nc):
+        raise ValueError("term_ce_fwd: x (rows, d), W (C, d), bias (C), labels (rows), class_w (C)")
+    dev = x.device
+    st = TermCE()
+    st.x, st.W = x, W
+    st.bias = bias.to(torch.float32).contiguous()
+    st.labels = labels.reshape(-1).to(torch.int64).contiguous()
+    st.class_w = None if class_w is None else class_w.to(torch.float32).contiguous()
+    st.ignore_index = int(ignore_index)
+    st.loss = torch.empty((), dtype=torch.float32, device=dev)
+    st.sums = torch.empty(2, dtype=torch.float32, device=dev)
+    need = int(L.lib.cg_term_ce_workspace(rows, d, min(nc, L.TERM_CE_MAX_CLASSES)))
+    ws = workspace
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    st.workspace = ws
+    p = _term_ce_desc(st)
+    p.loss, p.sums = st.loss.data_ptr(), st.sums.data_ptr()
+    L.check(L.lib.cg_term_ce_fwd(C.byref(p), L.stream_ptr(dev)), "cg_term_ce_fwd")
+    return st
+
+
+def term_ce_bwd(st: TermCE, *, scale=1.0, scale_dev=None, dW=None, db=None, dx=None, want=("dW", "db", "dx")):
+    """Backward of term_ce_fwd (cg_term_ce_bwd): g = scale * scale_dev * w_y (softmax - onehot) /
+    sum w on the labelled rows; dW (C, d) = g^T x, db (C) = column sums of g, dx (rows, d) = g W,
+    all fp32.  A tensor passed as dW / db / dx is ACCUMULATED into (and returned); an output named
+    in ``want`` and not passed is allocated and overwritten (dx: zero on unlabelled rows).
+    scale_dev: an optional one-element fp32 device tensor, read in the kernel.  Returns (dW, db, dx)
+    with None for outputs neither passed nor wanted."""
+    rows, d = st.x.shape
+    nc = st.W.shape[0]
+    dev = st.x.device
+    p = _term_ce_desc(st)
+    p.scale = float(scale)
+    if scale_dev is not None:
+        L.require_device(scale_dev, "term_ce_bwd")
+        scale_dev = scale_dev.detach().reshape(1).to(torch.float32).contiguous()
+        p.scale_dev = scale_dev.data_ptr()
+    shapes = {"dW": (nc, d), "db": (nc,), "dx": (rows, d)}
+    outs = {}
+    for name, t in (("dW", dW), ("db", db), ("dx", dx)):
+        acc = t is not None
+        if t is None and name in want:
+            t = torch.empty(shapes[name], dtype=torch.float32, device=dev)
+        outs[name] = t
+        if t is None:
+            continue
+        L.require_device(t, "term_ce_bwd")
+        if tuple(t.shape) != shapes[name]:
+            raise ValueError(f"term_ce_bwd: {name} must have shape {shapes[name]}")
+        setattr(p, name, t.data_ptr())
+        setattr(p, "acc_" + name, int(acc))
+        if name == "db":
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("term_ce_bwd: db must be contiguous fp32")
+        else:
+            setattr(p, "ld" + name.lower(), _rows2d(t, f"term_ce_bwd: {name}", (torch.float32,)))
+    L.check(L.lib.cg_term_ce_bwd(C.byref(p), L.stream_ptr(dev)), "cg_term_ce_bwd")
+    return outs["dW"], outs["db"], outs["dx"]

@@ -29,11 +29,23 @@ class FusedAdamW(torch.optim.Optimizer):
         fast, backbone = [], []
         for name, p in model.named_parameters():
             (fast if _is_fast(name) else backbone).append((name, p))
+        # only trainable parameters enter the groups (loop.py:685-698).  A group is a contiguous range
+        # of the flat buffer, so it is trainable or frozen as a whole: freeze_backbone (loop.py:656-667)
+        # leaves the fast group alone, and the launch then covers the tail range only -- frozen
+        # values, their moments and their weight decay are never touched
+        live = {}
+        for key, members in (("fast", fast), ("backbone", backbone)):
+            n_train = sum(1 for _, p in members if p.requires_grad)
+            if n_train not in (0, len(members)):
+                raise ValueError(f"FusedAdamW: the {key} parameter group must be trainable or frozen as a whole")
+            live[key] = n_train > 0
+        if not (live["fast"] or live["backbone"]):
+            raise ValueError("FusedAdamW: no trainable parameter")
         groups = []
-        if fast:
+        if live["fast"]:
             groups.append({"params": [p for _, p in fast], "lr": lr if lr_embedding is None else lr_embedding,
                            "weight_decay": 0.0})
-        if backbone:
+        if live["backbone"]:
             groups.append({"params": [p for _, p in backbone], "lr": lr, "weight_decay": weight_decay})
         super().__init__(groups, dict(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps))
         self.betas, self.eps = betas, eps
@@ -44,7 +56,7 @@ class FusedAdamW(torch.optim.Optimizer):
         fast_begin = min((p.data_ptr() - base) // 4 for _, p in fast) if fast else total
         if any((p.data_ptr() - base) // 4 >= fast_begin for _, p in backbone):
             raise RuntimeError("FusedAdamW: the fast parameter group is not the tail of the flat buffer")
-        self._ranges = [(fast_begin, total), (0, fast_begin)] if fast else [(0, total)]
+        self._ranges = ([(fast_begin, total)] if live["fast"] else []) + ([(0, fast_begin)] if live["backbone"] else [])
         self.exp_avg = torch.zeros_like(flat)
         self.exp_avg_sq = torch.zeros_like(flat)
         self.step_count = 0

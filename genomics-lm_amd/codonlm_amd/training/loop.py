@@ -34,9 +34,17 @@ wall-time decisions are one collective per microbatch over a CPU process group
 host reads the loss values once, through an event recorded after the forward, so the
 backward's kernels keep the GPU busy meanwhile; nothing else synchronises.
 
+* termination-head correction: ``freeze_backbone`` (loop.py:656-667) trains termination_head and
+  offset_projs alone -- the engine's heads-only backward, the termination loss from the fused
+  kernel and an AdamW launch over the aux parameters' range -- and ``replay_loss_enabled``
+  (loop.py:1113-1142, codonlm_amd/replay.py) adds, every ``replay_every_microbatches`` train
+  microbatches, ``replay_loss_weight`` times the fused termination loss of a replay batch: after
+  the main backward, a trunk-only forward, the fused loss and an accumulating backward.  Such
+  runs all-reduce at the end of the group (a frozen run the aux range only), not per bucket.
+
 Outside the MI355X hot path and rejected with a clear error: shape guidance / biophysics
-encoder, replay-termination loss, Adafactor, freeze_backbone, torch.compile (ignored: the
-engine is already native), dataset manifests (not enforced).
+encoder, Adafactor; torch.compile is ignored (the engine is already native) and dataset
+manifests are not enforced.
 """
 from __future__ import annotations
 
@@ -55,10 +63,12 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 import torch.distributed as dist
+from torch.utils.data import DataLoader
 
 from ..data_loading import DeviceBatchLoader, DeviceCodonDataset
 from ..model_tiny_gpt import TinyGPT
 from ..optim import FusedAdamW
+from ..replay import GeneratedTerminationReplayDataset
 from . import objectives as obj
 from .checkpoint import load_transfer_state_dict, transfer_source_itos
 from .ddp import DataParallelStep
@@ -327,9 +337,7 @@ def build_model(cfg: dict, device) -> TinyGPT:
 
 
 def _reject_out_of_scope(cfg: dict) -> None:
-    for key, what in (("use_shape_guidance", "shape guidance (biophysics encoder)"),
-                      ("replay_loss_enabled", "replay-termination loss"),
-                      ("freeze_backbone", "freeze_backbone")):
+    for key, what in (("use_shape_guidance", "shape guidance (biophysics encoder)"),):
         if bool(cfg.get(key, False)):
             raise NotImplementedError(f"{what} is outside the MI355X hot path")
     if str(cfg.get("optimizer", "adamw")).lower() != "adamw":
@@ -413,6 +421,22 @@ def run_training(cfg: dict, args) -> None:
             raise ValueError("termination_class_weights must contain termination_n_classes values")
         if any(float(v) <= 0 for v in term_cw_values):
             raise ValueError("termination_class_weights values must be positive")
+    # replay-termination loss (loop.py:360-393)
+    replay_enabled = bool(cfg.get("replay_loss_enabled", False))
+    replay_weight = float(cfg.get("replay_loss_weight", 0.1))
+    replay_data = cfg.get("replay_data")
+    replay_batch_size = int(cfg.get("replay_batch_size", cfg.get("batch_size", 1)))
+    replay_every = int(cfg.get("replay_every_microbatches", 1))
+    if replay_every <= 0:
+        raise ValueError("replay_every_microbatches must be positive")
+    replay_cw_values = cfg.get("replay_class_weights")
+    if replay_cw_values is not None:
+        if len(replay_cw_values) != term_n_classes:
+            raise ValueError("replay_class_weights must contain termination_n_classes values")
+        if any(float(v) <= 0 for v in replay_cw_values):
+            raise ValueError("replay_class_weights values must be positive")
+    if replay_enabled and not replay_data:
+        raise ValueError("replay_loss_enabled=true requires replay_data")
 
     run_id = (getattr(args, "run_id", None) or cfg.get("run_id") or os.environ.get(RUN_ID_ENV) or "").strip() or None
     if not run_id:
@@ -452,8 +476,9 @@ def run_training(cfg: dict, args) -> None:
             for o in sorted(multi_offset_weights):
                 offset_cols += [f"train_offset_{o}", f"val_offset_{o}"]
             term_cols = ["train_term_loss", "val_term_loss"] if term_enabled else []
+            replay_cols = ["train_replay_term_loss"] if replay_enabled else []
             csv.writer(f).writerow(["step", "train_loss", "val_loss", "train_next_loss", "val_next_loss",
-                                    "perplexity", "lr", *offset_cols, *term_cols])
+                                    "perplexity", "lr", *offset_cols, *term_cols, *replay_cols])
 
     torch.manual_seed(base_seed)
     model = build_model(cfg, device)
@@ -484,6 +509,45 @@ def run_training(cfg: dict, args) -> None:
                 print(f"[transfer] unexpected_after_adapt={report['unexpected']}")
     term_cw = (torch.tensor([float(v) for v in term_cw_values], dtype=torch.float32, device=device)
                if term_cw_values is not None else None)
+    replay_cw = (torch.tensor([float(v) for v in replay_cw_values], dtype=torch.float32, device=device)
+                 if replay_cw_values is not None else None)
+    replay_loader = None
+    if replay_enabled:  # loop.py:585-608
+        if is_main:
+            print(f"[loss] replay_termination weight={replay_weight} data={replay_data} "
+                  f"batch_size={replay_batch_size} every_microbatches={replay_every} "
+                  f"class_weights={replay_cw_values}")
+        replay_path = Path(str(replay_data))
+        if not replay_path.is_absolute():
+            replay_path = Path.cwd() / replay_path
+        replay_ds = GeneratedTerminationReplayDataset(replay_path, block_size=int(cfg["block_size"]), pad_id=PAD_ID,
+                                                      n_classes=term_n_classes)
+        replay_generator = torch.Generator()
+        # every rank draws its own replay batches; world = 1 reproduces the reference's order
+        replay_generator.manual_seed(base_seed + 17 + (rank if world > 1 else 0))
+        replay_loader = DataLoader(replay_ds, batch_size=max(1, replay_batch_size), shuffle=True, num_workers=0,
+                                   drop_last=False, generator=replay_generator)
+        cfg["replay_data"] = str(replay_path)
+        cfg["replay_examples"] = int(len(replay_ds))
+        if is_main:
+            print(f"[replay] loaded {len(replay_ds)} generated-state records from {replay_path}")
+    replay_state = {"iter": None}
+    freeze_backbone = bool(cfg.get("freeze_backbone", False))
+    if freeze_backbone:  # loop.py:656-667; before the optimizer, which takes trainable parameters only
+        n_frozen = n_trainable = 0
+        for name, param in model.named_parameters():
+            keep = "offset_projs" in name or "termination_head" in name
+            param.requires_grad_(keep)
+            n_trainable += int(keep)
+            n_frozen += int(not keep)
+        if n_trainable == 0:
+            raise ValueError("freeze_backbone=true leaves nothing to train: the model has no termination_head "
+                             "or offset_projs (enable termination_loss_enabled, replay_loss_enabled or "
+                             "multi_offset_loss_enabled)")
+        model.zero_grad()
+        if is_main:
+            print(f"[freeze] Backbone frozen: {n_frozen} tensors frozen, {n_trainable} tensors trainable "
+                  "(offset_projs and termination_head)")
     lr_base = float(cfg.get("lr", 5e-6))
     optim = FusedAdamW(model, lr=lr_base, weight_decay=float(cfg.get("weight_decay", 0.05)),
                        lr_embedding=float(cfg.get("lr_embedding", lr_base)))
@@ -565,14 +629,14 @@ def run_training(cfg: dict, args) -> None:
     last_saved = {"step": st.step, "t": time.monotonic()}
 
     def payload(epoch_idx, train_loss=float("inf"), val_loss=float("inf"), train_next_loss=None,
-                val_next_loss=None, train_term_loss=None, val_term_loss=None) -> dict:
+                val_next_loss=None, train_term_loss=None, val_term_loss=None, train_replay_term_loss=None) -> dict:
         done = val_loss != float("inf")
         return {
             "model": model.state_dict(), "optimizer": optim.state_dict(),
             "scheduler": scheduler.state_dict() if scheduler is not None else None, "cfg": _plain(cfg),
             "epoch": epoch_idx if done else max(0, epoch_idx - 1), "val_loss": val_loss, "train_loss": train_loss,
             "train_next_loss": train_next_loss, "val_next_loss": val_next_loss, "train_term_loss": train_term_loss,
-            "val_term_loss": val_term_loss, "train_replay_term_loss": None, "best_val": st.best,
+            "val_term_loss": val_term_loss, "train_replay_term_loss": train_replay_term_loss, "best_val": st.best,
             "best_epoch": st.best_epoch, "no_improve": st.no_improve, "step": st.step,
             "consumed_train_tokens": int(st.consumed), "runtime_memory": {},
             "epoch_microbatch_idx": 0 if done else int(st.cur_resume_mb),
@@ -591,7 +655,14 @@ def run_training(cfg: dict, args) -> None:
         if is_main:
             save_checkpoint_atomic(p, ckpt_dir / name)
 
-    dp = DataParallelStep(model, optim) if world > 1 else None
+    # bucketed all-reduce inside the last backward of a group: not with a replay backward in the
+    # group (the main backward is then not the group's last) nor with a frozen backbone (no block
+    # buckets); those runs all-reduce once at the end of the group
+    dp = DataParallelStep(model, optim) if world > 1 and not (replay_enabled or freeze_backbone) else None
+    aux_begin = None
+    if freeze_backbone:  # the aux parameters' range of the flat buffer (its tail)
+        base_ptr = model.flat_parameters().data_ptr()
+        aux_begin = min((p.data_ptr() - base_ptr) // 4 for p in model.parameters() if p.requires_grad)
     wall_limit = cfg.get("max_time_minutes")
     t_wall0 = time.perf_counter()
     ctl = GroupController(gacc=gacc, health=accumulation_health, world=world, group=ctrl,
@@ -599,13 +670,21 @@ def run_training(cfg: dict, args) -> None:
     # class weights of the next-codon loss, once (the reference checks torch.all(w == 1) per step)
     offset_lw = model.loss_weights if not bool(torch.all(model.loss_weights == 1.0)) else None
     offset_keys = sorted(multi_offset_weights)
-    stats_host = torch.empty(4 + 2 * len(offset_keys), dtype=torch.float32, pin_memory=True)
+    stats_host = torch.empty(5 + 2 * len(offset_keys), dtype=torch.float32, pin_memory=True)
 
     def forward_objective(xb, yb):
         """The trainer's objective (loop.py:1075-1112) as device tensors: (total, next, term or
         None, {offset: loss}, {offset: n_valid})."""
         need_aux = term_enabled or bool(multi_offset_weights)
-        if need_aux:
+        # a frozen backbone takes the termination loss from the fused kernel (no logits); an
+        # unfrozen run keeps the dense path
+        term_labels = None
+        if term_enabled:
+            term_labels = obj.termination_distance_bucket_labels(yb, stop_ids=term_stop_ids, bucket_edges=term_edges)
+        if term_enabled and freeze_backbone:
+            logits, next_loss, aux = model(xb, yb, return_aux=True, termination_labels=term_labels,
+                                           termination_class_weights=term_cw)
+        elif need_aux:
             logits, next_loss, aux = model(xb, yb, return_aux=True)
         else:
             logits, next_loss = model(xb, yb)
@@ -619,12 +698,29 @@ def run_training(cfg: dict, args) -> None:
             total = total + off_total
         term_loss = None
         if term_enabled:
-            labels = obj.termination_distance_bucket_labels(yb, stop_ids=term_stop_ids, bucket_edges=term_edges)
-            term_loss = obj.termination_aux_loss(aux["termination_logits"], labels, class_weights=term_cw)
+            if "termination_loss" in aux:
+                term_loss = aux["termination_loss"]
+            else:
+                term_loss = obj.termination_aux_loss(aux["termination_logits"], term_labels, class_weights=term_cw)
             total = total + term_weight * term_loss
         return total, next_loss, term_loss, offset_losses, offset_counts
 
-    def read_stats(total, next_loss, term_loss, off_losses, off_counts, yb):
+    def replay_objective():
+        """The replay batch of this microbatch (loop.py:1113-1142): the next batch of the replay
+        loader (restarted when exhausted), a trunk-only forward and the fused termination loss
+        on its sparse labels."""
+        if replay_state["iter"] is None:
+            replay_state["iter"] = iter(replay_loader)
+        try:
+            rx, rlabels = next(replay_state["iter"])
+        except StopIteration:
+            replay_state["iter"] = iter(replay_loader)
+            rx, rlabels = next(replay_state["iter"])
+        _, _, raux = model(rx.to(device), return_aux=True, termination_labels=rlabels.to(device),
+                           termination_class_weights=replay_cw, head=False)
+        return raux["termination_loss"]
+
+    def read_stats(total, next_loss, term_loss, off_losses, off_counts, yb, replay_loss=None):
         """One device->host transfer of the microbatch's scalars, recorded right after the
         forward: the caller enqueues the backward and then waits on the returned event only,
         so the backward's kernels run while the host decides."""
@@ -635,6 +731,8 @@ def run_training(cfg: dict, args) -> None:
             parts.append(off_losses[k].detach().float().reshape(1) if k in off_losses
                          else torch.zeros(1, device=device))
             parts.append(off_counts[k].float().reshape(1) if k in off_counts else torch.zeros(1, device=device))
+        if replay_loss is not None:  # last: the layout of the other entries does not move
+            parts.append(replay_loss.detach().float().reshape(1))
         host = stats_host[: len(parts)]
         host.copy_(torch.cat(parts), non_blocking=True)
         ev = torch.cuda.Event()
@@ -659,6 +757,7 @@ def run_training(cfg: dict, args) -> None:
         else:
             total, next_total, n = 0.0, 0.0, 0
         term_total, term_count = 0.0, 0
+        replay_total, replay_count = 0.0, 0
         off_tot = {o: 0.0 for o in multi_offset_weights}
         off_cnt = {o: 0 for o in multi_offset_weights}
         optim.zero_grad(set_to_none=True)
@@ -678,6 +777,8 @@ def run_training(cfg: dict, args) -> None:
             if world > 1:
                 if handles:
                     drain()  # the buckets were all-reduced during this microbatch's backward
+                elif aux_begin is not None:  # frozen backbone: only the aux range holds gradients
+                    dist.all_reduce(model.flat_grads()[aux_begin:], op=dist.ReduceOp.SUM)
                 else:
                     dist.all_reduce(model.flat_grads(), op=dist.ReduceOp.SUM)
             if (not use_cosine) and warmup_steps > 0 and st.step < warmup_steps:
@@ -708,15 +809,28 @@ def run_training(cfg: dict, args) -> None:
             st.cur_mb = batch_idx + 1
             with torch.set_grad_enabled(train):
                 loss, next_loss, term_loss, off_losses, off_counts = forward_objective(xb, yb)
-            host, ev = read_stats(loss, next_loss, term_loss, off_losses, off_counts, yb)
-            if train:
-                # backward enqueued before the finiteness verdict: a nonfinite microbatch aborts
-                # its whole group, whose gradients are then discarded anyway (loop.py:1197-1219)
-                if dp is not None and ctl.completes_group(batch_idx == shard - 1):
-                    model._bucket_hook = dp.bucket_hook(handles)
+            replay_loss = None
+            if train and replay_loader is not None and (batch_idx + 1) % replay_every == 0:
+                # a replay microbatch: the main backward first (the replay forward reuses the
+                # engine's activations), then the replay batch's trunk-only forward and fused loss;
+                # its weighted loss joins the total before the one stats transfer and the verdict
                 loss.backward()
+                replay_loss = replay_objective()
+                weighted = replay_weight * replay_loss
+                host, ev = read_stats(loss.detach() + weighted.detach(), next_loss, term_loss, off_losses, off_counts,
+                                      yb, replay_loss)
+                weighted.backward()
+            else:
+                host, ev = read_stats(loss, next_loss, term_loss, off_losses, off_counts, yb)
+                if train:
+                    # backward enqueued before the finiteness verdict: a nonfinite microbatch aborts
+                    # its whole group, whose gradients are then discarded anyway (loop.py:1197-1219)
+                    if dp is not None and ctl.completes_group(batch_idx == shard - 1):
+                        model._bucket_hook = dp.bucket_hook(handles)
+                    loss.backward()
             ev.synchronize()
             vals = unpack(host)
+            v_replay = host[-1].item() if replay_loss is not None else None
             if train:
                 abort, stop = ctl.agree(not math.isfinite(vals[0]))
             else:
@@ -757,6 +871,9 @@ def run_training(cfg: dict, args) -> None:
             if term_loss is not None:
                 term_total += v_term
                 term_count += 1
+            if v_replay is not None:
+                replay_total += v_replay
+                replay_count += 1
             for o, val in v_offs.items():
                 off_tot[o] += val
                 off_cnt[o] += 1
@@ -784,7 +901,8 @@ def run_training(cfg: dict, args) -> None:
         health_after = accumulation_health.state_dict()
         return (total / max(n, 1), next_total / max(n, 1),
                 (term_total / max(term_count, 1)) if term_enabled else None, skipped, offset_avgs,
-                {k: health_after[k] - health_before[k] for k in health_after})
+                {k: health_after[k] - health_before[k] for k in health_after},
+                (replay_total / max(replay_count, 1)) if replay_enabled and train else None)
 
     history = []
     try:
@@ -795,10 +913,10 @@ def run_training(cfg: dict, args) -> None:
             if skip == 0:
                 epoch_metrics.update(total_loss_sum=0.0, next_loss_sum=0.0, microbatches=0, initial_loss=None)
                 pending_metrics.update(total_loss_sum=0.0, next_loss_sum=0.0, microbatches=0, initial_loss=None)
-            tr_loss, tr_next, tr_term, tr_skips, tr_offs, tr_health = one_pass("train", train_loader_for(epoch + 1),
-                                                                               epoch_idx, skip)
+            tr_loss, tr_next, tr_term, tr_skips, tr_offs, tr_health, tr_replay = one_pass(
+                "train", train_loader_for(epoch + 1), epoch_idx, skip)
             with torch.no_grad():
-                va_loss, va_next, va_term, va_skips, va_offs, _ = one_pass("val", val_loader(), epoch_idx)
+                va_loss, va_next, va_term, va_skips, va_offs, _, _ = one_pass("val", val_loader(), epoch_idx)
             ppl = math.exp(min(20.0, va_next))
             if not use_cosine:
                 scheduler.step(va_loss)
@@ -806,6 +924,8 @@ def run_training(cfg: dict, args) -> None:
             if is_main:
                 msg = (f"[epoch {epoch_idx}] train {tr_loss:.3f} | val {va_loss:.3f} | next_val {va_next:.3f} "
                        f"| ppl {ppl:.2f} | lr {lr_now:.2e}")
+                if tr_replay is not None:
+                    msg += f" | replay_term train={tr_replay:.3f}"
                 if tr_skips or va_skips:
                     msg += f" | skips train={tr_skips} val={va_skips}"
                 print(msg)
@@ -814,7 +934,7 @@ def run_training(cfg: dict, args) -> None:
                 st.best, st.best_epoch, st.no_improve = va_loss, epoch_idx, 0
             else:
                 st.no_improve += 1
-            p = payload(epoch_idx, tr_loss, va_loss, tr_next, va_next, tr_term, va_term)
+            p = payload(epoch_idx, tr_loss, va_loss, tr_next, va_next, tr_term, va_term, tr_replay)
             save(p, "last.pt")
             last_saved.update(step=st.step, t=time.monotonic())
             if cfg.get("save_epochs", False):
@@ -827,10 +947,12 @@ def run_training(cfg: dict, args) -> None:
                         row += [f"{tr_offs.get(o, 0.0):.4f}", f"{va_offs.get(o, 0.0):.4f}"]
                     if term_enabled:
                         row += [f"{tr_term:.4f}", f"{va_term:.4f}"]
+                    if replay_enabled:
+                        row.append(f"{tr_replay:.4f}")
                     csv.writer(f).writerow(row)
             history.append({"epoch": epoch_idx, "train_loss": tr_loss, "val_loss": va_loss,
                             "train_next_loss": tr_next, "val_next_loss": va_next, "train_term_loss": tr_term,
-                            "val_term_loss": va_term, "train_replay_term_loss": None, "perplexity": ppl,
+                            "val_term_loss": va_term, "train_replay_term_loss": tr_replay, "perplexity": ppl,
                             "lr": lr_now, "nonfinite_microbatches": tr_health["nonfinite_microbatches"],
                             "aborted_accumulation_groups": tr_health["aborted_groups"],
                             "discarded_finite_microbatches": tr_health["discarded_finite_microbatches"]})
@@ -919,7 +1041,8 @@ def _finish(is_main, ckpt_dir, scores_dir, run_id, t_wall0, st, health, model, h
         meta.update({"last_epoch": h["epoch"], "last_val_loss": h["val_loss"], "last_train_loss": h["train_loss"],
                      "last_val_next_loss": h["val_next_loss"], "last_train_next_loss": h["train_next_loss"],
                      "last_val_term_loss": h["val_term_loss"], "last_train_term_loss": h["train_term_loss"],
-                     "last_train_replay_term_loss": None, "last_perplexity": h["perplexity"]})
+                     "last_train_replay_term_loss": h.get("train_replay_term_loss"),
+                     "last_perplexity": h["perplexity"]})
         (scores_dir / "metrics.json").write_text(json.dumps(meta, indent=2) + "\n")
     write_meta(ckpt_dir, meta)
 

@@ -256,7 +256,7 @@ struct DwSlot {
 };
 // byte sizes of the carved scratch buffers handed to the op entry points (their ws_bytes)
 struct WsBytes {
-  size_t lnp, cpart, colws, splitws, embws, cews, delta, ocp_half, dwslab;
+  size_t lnp, cpart, colws, splitws, embws, cews, delta, ocp_half, dwslab, termws;
 };
 struct Acts {
   int32_t* seg;
@@ -285,6 +285,8 @@ struct Acts {
   // the tied head's weight gradient over all heads is ONE product reduced over heads x tokens
   std::vector<void*> odl;
   std::vector<float*> ocp;  // their bias-gradient column-sum partials (2 per head), reduced batched
+  // cg_term_ce_fwd's per-row state, kept from cg_model_term_loss to the backward (nothing else uses it)
+  void* termws;
 };
 
 constexpr int MAX_SPLIT = 16;
@@ -420,6 +422,8 @@ size_t carve(const cg_model_cfg* c, const Dims& D, int B, int T, char* base, Act
   const bool dmask = c->dtype == CG_BF16 && c->dropout > 0.f;
   for (int l = 0; l < D.L; ++l)
     A.la[l].dmask = dmask ? w.take<char>(cg_attn_drop_mask_bytes(B, T, D.H)) : nullptr;
+  A.nb.termws = c->termination_aux ? cg_term_ce_workspace(M, d, c->termination_n_classes) : 0;
+  A.termws = A.nb.termws ? w.take<char>(A.nb.termws) : nullptr;
   return w.off + 256;
 }
 
@@ -773,10 +777,28 @@ int zero_grad(const Ctx& C, long long off, long long elems) {
   return hipMemsetAsync(G(C, off), 0, (size_t)elems * 4, C.s) == hipSuccess ? CG_OK : CG_ELAUNCH;
 }
 
+// the fused termination loss over the ln_f output of the last forward (cg_term_ce_fwd / _bwd): the
+// operands both directions share; the head's fp32 master weights in either compute dtype
+cg_term_ce_desc term_desc(const Ctx& C) {
+  const cg_model* m = C.m;
+  cg_term_ce_desc t;
+  memset(&t, 0, sizeof(t));
+  t.x_dtype = C.dt; t.x = C.A.xf; t.ldx = C.D.d;
+  t.rows = C.M; t.d = C.D.d; t.C = m->cfg.termination_n_classes;
+  t.W = P(C, C.Lo.termw); t.ldw = C.D.d;
+  t.bias = P(C, C.Lo.termb);
+  t.labels = m->term_labels; t.ignore_index = -100;
+  t.class_w = m->term_class_w;
+  t.workspace = C.A.termws; t.ws_bytes = C.A.nb.termws;
+  return t;
+}
+
 // Backward of the auxiliary heads (model_tiny_gpt.py:329-337) inside phase 0: parameter grads
 // of termination_head / offset_projs, the tied head's extra gradient, and their share of dxf
 // (added into A.dtmp before the ln_f backward).  A.dlogits is free here (head products done).
-int aux_backward(const Ctx& C, int accumulate) {
+// heads_only (cg_model_backward_heads): the aux parameters' gradients alone -- no d(head) product,
+// no dxf product, no transposed weight copies (they were not refreshed).
+int aux_backward(const Ctx& C, int accumulate, bool heads_only) {
   const cg_model* m = C.m;
   const Dims& D = C.D;
   const Acts& A = C.A;
@@ -792,7 +814,19 @@ int aux_backward(const Ctx& C, int accumulate) {
   grp.tile_m = 128;  // 10 products of d x d at C5: the 128-row tile gives the most workgroups
   if (m->cfg.termination_aux) {
     const int nc = m->cfg.termination_n_classes, ncp = (int)rup(nc, 16);
-    if (m->d_term_logits) {
+    if (m->term_fused) {
+      // the fused loss's backward over the labelled rows: dW_t, db_t and dxf += g . W_t
+      if (m->d_term_logits || !m->term_labels) return CG_EINVAL;
+      cg_term_ce_desc t = term_desc(C);
+      t.scale = m->term_scale; t.scale_dev = m->term_scale_dev;
+      t.dW = G(C, C.Lo.termw); t.lddw = d; t.acc_dW = accumulate;
+      t.db = G(C, C.Lo.termb); t.acc_db = accumulate;
+      if (!heads_only) {
+        t.dx = A.dtmp; t.lddx = d; t.acc_dx = 1;
+      }
+      CK(cg_term_ce_bwd(&t, C.s));
+      if (!accumulate && ncp > nc) CK(zero_grad(C, C.Lo.termw + (long long)nc * d, (long long)(ncp - nc) * d));
+    } else if (m->d_term_logits) {
       if (!m->aux_ready || m->ld_d_term < nc) return CG_EINVAL;
       CK(cg_cast_pad_2d(m->d_term_logits, m->ld_d_term, (int)M, nc, C.dt, A.dlogits, ncp, ncp, C.s));
       // dW_t = dT^T . xf over the padded rows (pad rows of dT^T are zero): bf16 in the grouped launch
@@ -819,12 +853,14 @@ int aux_backward(const Ctx& C, int accumulate) {
       }
       CK(cg_colsum(CG_F32, m->d_term_logits, m->ld_d_term, (int)M, nc, G(C, C.Lo.termb), accumulate, A.colws,
                    A.nb.colws, C.s));
-      cg_gemm_desc g = gdesc(C);
-      // dxf += dT . W_t
-      g = lin_dx(C, A.dlogits, ncp, C.Lo.termw, d, ncp, d, A.dtmp, d);
-      g.c_dtype = CG_F32;
-      g.epilogue = CG_EPI_RESID; g.resid = A.dtmp; g.ldr = d;
-      CK(cg_gemm(&g, C.s));
+      if (!heads_only) {
+        cg_gemm_desc g = gdesc(C);
+        // dxf += dT . W_t
+        g = lin_dx(C, A.dlogits, ncp, C.Lo.termw, d, ncp, d, A.dtmp, d);
+        g.c_dtype = CG_F32;
+        g.epilogue = CG_EPI_RESID; g.resid = A.dtmp; g.ldr = d;
+        CK(cg_gemm(&g, C.s));
+      }
     } else if (!accumulate) {
       CK(zero_grad(C, C.Lo.termw, (long long)ncp * d));
       CK(zero_grad(C, C.Lo.termb, nc));
@@ -864,12 +900,13 @@ int aux_backward(const Ctx& C, int accumulate) {
     CK(add_dw(dpj, A.og[i], C.Lo.off2w[i]));
     CK(defer_colsum(C, dpj, A.ocp[i], C.Lo.off2b[i], accumulate));
     // da = (dpj . W2) * gelu'(a) ; the first Linear's grads
-    const bool hasT = i < (int)A.o2T.size();
+    const bool hasT = !heads_only && i < (int)A.o2T.size();
     g = lin_dx(C, dpj, d, C.Lo.off2w[i], d, d, d, da, d, hasT ? A.o2T[i] : nullptr);
     g.epilogue = CG_EPI_DGELU | CG_EPI_GELU_DERIV; g.aux = A.oa[i]; g.ld_aux = d;
     CK(cg_gemm(&g, C.s));
     CK(add_dw(da, A.xf, C.Lo.off1w[i]));
     CK(defer_colsum(C, da, A.ocp[i] + cg_colsum_workspace((int)M, d) / 4, C.Lo.off1b[i], accumulate));
+    if (heads_only) continue;
     // dxf += da . W1
     g = lin_dx(C, da, d, C.Lo.off1w[i], d, d, d, A.dtmp, d, hasT ? A.o1T[i] : nullptr);
     g.c_dtype = CG_F32;
@@ -879,7 +916,7 @@ int aux_backward(const Ctx& C, int accumulate) {
   // d(head) += sum_i Gc_i^T . pj_i over the heads with a gradient: one product reduced over
   // (head, token) rows -- the logits gradients and pj operands are stacked per head (phase 0's own
   // head product initialised it; hi half of split rows)
-  for (int first = 0; first < noff;) {  // one product per run of consecutive heads with a gradient
+  for (int first = 0; first < noff && !heads_only;) {  // one product per run of consecutive heads with a gradient
     if (!m->d_offset_logits[first]) {
       ++first;
       continue;
@@ -952,8 +989,11 @@ extern "C" size_t cg_model_workspace_bytes(const cg_model_cfg* cfg, int B, int T
   return carve(cfg, D, B, T, nullptr, A);
 }
 
-extern "C" int cg_model_forward(cg_model* m, const int64_t* idx, const int64_t* targets, int B, int T, int training,
-                                uint32_t seed, int window, float* logits, float* loss, void* stream) {
+namespace {
+// cg_model_forward (head = true) and cg_model_forward_trunk (head = false: through ln_f, no head
+// product, no logits, no cross-entropy)
+int forward_body(cg_model* m, const int64_t* idx, const int64_t* targets, int B, int T, int training, uint32_t seed,
+                 int window, float* logits, float* loss, void* stream, bool head) {
   if (!m || !idx || B <= 0 || T <= 0) return CG_EINVAL;
   if (T > m->cfg.block_size) return CG_EINVAL;
   if (m->cfg.dtype == CG_BF16 && !m->shadow) return CG_EINVAL;
@@ -963,6 +1003,8 @@ extern "C" int cg_model_forward(cg_model* m, const int64_t* idx, const int64_t* 
   m->aux_ready = 0; m->head_grad_scale = 1.0f; m->head_grad_scale_dev = nullptr;
   m->d_term_logits = nullptr; m->ld_d_term = 0;
   for (int i = 0; i < 8; ++i) m->d_offset_logits[i] = nullptr;
+  m->term_fused = 0; m->term_labels = nullptr; m->term_class_w = nullptr;
+  m->term_scale = 1.0f; m->term_scale_dev = nullptr;
   Ctx C;
   CK(make_ctx(m, B, T, stream, C));
   const Dims& D = C.D;
@@ -971,7 +1013,7 @@ extern "C" int cg_model_forward(cg_model* m, const int64_t* idx, const int64_t* 
   const long long M = C.M;
   const float p = train_p(m);
   const float eps = m->cfg.ln_eps > 0 ? m->cfg.ln_eps : 1e-5f;
-  m->logits = logits ? logits : A.logits_int;
+  m->logits = !head ? nullptr : logits ? logits : A.logits_int;
 
   // the attention keep bits: written by each block's attention forward itself (default), or by the
   // mask kernel right before it (cfg.opts.attn_mask_kernel; a mask pass on a side stream ahead of
@@ -1056,6 +1098,7 @@ extern "C" int cg_model_forward(cg_model* m, const int64_t* idx, const int64_t* 
   }
   float* xL = A.x + (size_t)D.L * M * d;
   CK(cg_layernorm_fwd(C.dt, xL, d, P(C, C.Lo.lnfw), P(C, C.Lo.lnfb), A.xf, d, A.meanf, A.rstdf, (int)M, d, eps, C.s));
+  if (!head) return CG_OK;
   const long long hoff = m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head;
   // the head product runs at N = Vp (zero weight rows V..Vp-1) so that it takes the vector
   // epilogue tiles; the loss reads the padded logits and the caller's (M, V) copy is compacted
@@ -1069,11 +1112,39 @@ extern "C" int cg_model_forward(cg_model* m, const int64_t* idx, const int64_t* 
   }
   return CG_OK;
 }
+}  // namespace
+
+extern "C" int cg_model_forward(cg_model* m, const int64_t* idx, const int64_t* targets, int B, int T, int training,
+                                uint32_t seed, int window, float* logits, float* loss, void* stream) {
+  return forward_body(m, idx, targets, B, T, training, seed, window, logits, loss, stream, true);
+}
+
+extern "C" int cg_model_forward_trunk(cg_model* m, const int64_t* idx, int B, int T, int training, uint32_t seed,
+                                      int window, void* stream) {
+  return forward_body(m, idx, nullptr, B, T, training, seed, window, nullptr, nullptr, stream, false);
+}
+
+extern "C" int cg_model_term_loss(cg_model* m, const int64_t* labels, const float* class_w, float* loss,
+                                  void* stream) {
+  if (!m || !m->idx || m->B <= 0 || m->T <= 0 || !labels || !m->cfg.termination_aux) return CG_EINVAL;
+  Ctx C;
+  CK(make_ctx(m, m->B, m->T, stream, C));
+  m->term_labels = labels;
+  m->term_class_w = class_w;
+  cg_term_ce_desc t = term_desc(C);
+  t.loss = loss;
+  CK(cg_term_ce_fwd(&t, C.s));
+  m->term_fused = 1;
+  m->term_scale = 1.0f;
+  m->term_scale_dev = nullptr;
+  return CG_OK;
+}
 
 extern "C" int cg_model_aux_forward(cg_model* m, float* term_logits, long long ld_term, float* const* offset_logits,
                                     long long ld_off, void* stream) {
   if (!m || !m->idx || m->B <= 0 || m->T <= 0) return CG_EINVAL;
-  const int nc = m->cfg.termination_aux ? m->cfg.termination_n_classes : 0;
+  // after cg_model_term_loss the termination logits are optional (the fused loss does not need them)
+  const int nc = m->cfg.termination_aux && !(m->term_fused && !term_logits) ? m->cfg.termination_n_classes : 0;
   const int noff = std::min(m->cfg.n_offsets, 8);
   if (nc > 0 && (!term_logits || ld_term < nc)) return CG_EINVAL;
   if (noff > 0 && (!offset_logits || ld_off < m->cfg.vocab_size)) return CG_EINVAL;
@@ -1172,11 +1243,11 @@ extern "C" int cg_model_backward(cg_model* m, int phase, int layer, int accumula
       CK(cg_gemm(&g, C.s));
     } else {
       // no next-codon loss (aux-only objective, e.g. a replay batch): nothing to scale
-      if (m->head_grad_scale != 0.f || !m->aux_ready) return CG_EINVAL;
+      if (m->head_grad_scale != 0.f || (!m->aux_ready && !m->term_fused)) return CG_EINVAL;
       if (!accumulate) CK(zero_grad(C, hoff, (long long)D.Vp * d));
       if (hipMemsetAsync(A.dtmp, 0, (size_t)M * d * 4, C.s) != hipSuccess) return CG_ELAUNCH;
     }
-    CK(aux_backward(C, accumulate));  // aux heads add into d(head) and dxf
+    CK(aux_backward(C, accumulate, false));  // aux heads add into d(head) and dxf
     float* xL = A.x + (size_t)D.L * M * d;
     const int ll = D.L - 1;
     // gT feeds block L-1's MLP output Linear: its bias gradient (GELU mode) is gT's column sum
@@ -1293,13 +1364,28 @@ extern "C" int cg_model_backward(cg_model* m, int phase, int layer, int accumula
   return CG_EINVAL;
 }
 
+// The backward of a frozen backbone (loop.py:656-667): aux_backward's parameter gradients alone.  The
+// head weight is an operand of the offset heads' dpj product only (bf16: its split copy, fill_head2).
+extern "C" int cg_model_backward_heads(cg_model* m, int accumulate, void* stream) {
+  if (!m || !m->idx || !m->grads) return CG_EINVAL;
+  Ctx C;
+  CK(make_ctx(m, m->B, m->T, stream, C));
+  pending(m).n = 0;
+  m->head_dw_pending = 0;
+  bool any_off = false;
+  for (int i = 0; i < std::min(m->cfg.n_offsets, 8); ++i) any_off = any_off || m->d_offset_logits[i];
+  if (any_off) CK(fill_head2(C, m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head));
+  CK(aux_backward(C, accumulate, true));
+  return flush_reduce(m, C.s);
+}
+
 // Input attribution (scripts/analyze_saliency.py:48-81): the gradient of a seeded objective at the
 // embedding output of the last eval forward and its per-token reductions.  The dX chain of
 // cg_model_backward alone, with the same kernels and operands: no dW product, no bias column sum,
 // no parameter reduction, no embedding scatter, nothing written to m->grads or to the model's
 // backward state.  No block's operands outlive the block here, so slot 0 serves every block.
 extern "C" int cg_model_input_grad(cg_model* m, const cg_attr_desc* a, void* stream) {
-  if (!m || !a || !m->idx || m->B <= 0 || m->T <= 0 || m->training) return CG_EINVAL;
+  if (!m || !a || !m->idx || !m->logits || m->B <= 0 || m->T <= 0 || m->training) return CG_EINVAL;
   if (a->y ? (a->mode != CG_ATTR_LOGPROB && a->mode != CG_ATTR_LOGIT) : !m->targets) return CG_EINVAL;
   if (a->dx0 && a->ld_dx0 < m->cfg.n_embd) return CG_EINVAL;
   if (m->cfg.dtype == CG_BF16 && !m->shadow) return CG_EINVAL;
@@ -1758,7 +1844,7 @@ extern "C" size_t cg_struct_bytes(const char* name) {
   CG_SZ(cg_transpose_item) CG_SZ(cg_transpose_batch) CG_SZ(cg_adamw_segment) CG_SZ(cg_model_cfg)
   CG_SZ(cg_param_entry) CG_SZ(cg_model) CG_SZ(cg_model_opts) CG_SZ(cg_sample_params) CG_SZ(cg_gen_state)
   CG_SZ(cg_score_desc) CG_SZ(cg_sample_plan) CG_SZ(cg_offset_prior) CG_SZ(cg_attr_desc)
-  CG_SZ(cg_kmeans_desc)
+  CG_SZ(cg_kmeans_desc) CG_SZ(cg_term_ce_desc)
 #undef CG_SZ
   return 0;
 }

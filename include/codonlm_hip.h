@@ -485,6 +485,15 @@ typedef struct {
   /* engine-private: the parameter / bias gradient column reductions deferred to the end of the
    * current dW group (one cg_reduce_columns launch per group) */
   cg_reduce_batch reduce_pending;
+  /* termination-loss additions (zero-initialise).  cg_model_term_loss sets term_fused and the two
+   * pointers; between it and the backward the caller may set term_scale (host, 1 by default) and
+   * term_scale_dev (an optional device float multiplying it), the way head_grad_scale /
+   * head_grad_scale_dev scale the next-codon gradient.  Every forward resets all five. */
+  int term_fused;
+  const int64_t* term_labels;
+  const float* term_class_w;
+  float term_scale;
+  const float* term_scale_dev;
 } cg_model;
 
 /* forward: logits (fp32 [B*T][V] contiguous; NULL => internal buffer), loss (device
@@ -493,12 +502,27 @@ typedef struct {
 int cg_model_forward(cg_model* m, const int64_t* idx, const int64_t* targets, int B, int T,
                      int training, uint32_t seed, int window, float* logits, float* loss,
                      void* stream);
+/* the same forward through ln_f and no further: no head product, no logits, no cross-entropy
+ * (m->logits and m->targets are NULL afterwards).  cg_model_aux_forward, cg_model_term_loss,
+ * cg_model_hidden and the backward work after it as after a forward without targets: the second
+ * forward of a replay microbatch (loop.py:1113-1142), whose only loss sits on the termination head. */
+int cg_model_forward_trunk(cg_model* m, const int64_t* idx, int B, int T, int training, uint32_t seed,
+                           int window, void* stream);
+/* termination_aux_loss (objectives.py:94-105, ignore_index -100) of the termination head on the ln_f
+ * output of the last forward, without the logits: cg_term_ce_fwd with the fp32 master head weights.
+ * labels device int64 [B*T], class_w fp32 [termination_n_classes] or NULL, loss a device float; both
+ * arrays must stay alive until the backward.  It marks the model (term_fused) so that the backward's
+ * aux step runs cg_term_ce_bwd -- the head's weight and bias gradients and dxf += -- instead of the
+ * dense path over d_term_logits; setting d_term_logits as well makes the backward return CG_EINVAL.
+ * CG_EINVAL: no termination head, no forward yet, NULL labels. */
+int cg_model_term_loss(cg_model* m, const int64_t* labels, const float* class_w, float* loss, void* stream);
 /* auxiliary heads on the ln_f output of the last forward (model_tiny_gpt.py:329-337):
  * termination logits fp32 [B*T][ld_term] = xf W_t^T + b_t (termination_aux), and per
  * offset head i: logits_i fp32 [B*T][ld_off] = head(W2 gelu(W1 xf + b1) + b2) (tied head);
  * ld_off >= V; with ld_off >= round_up(V, 16) the zero pad columns are computed too (the
  * product then takes the vector / persistent GEMM tiles).
- * The offset activations stay in the workspace for the backward. */
+ * The offset activations stay in the workspace for the backward.  After cg_model_term_loss
+ * term_logits may be NULL: the termination logits are then not computed. */
 int cg_model_aux_forward(cg_model* m, float* term_logits, long long ld_term,
                          float* const* offset_logits, long long ld_off, void* stream);
 /* backward in phases so the caller can overlap per-bucket gradient all-reduce:
@@ -509,6 +533,13 @@ int cg_model_aux_forward(cg_model* m, float* term_logits, long long ld_term,
  *   parameters without a gradient are zeroed when accumulate=0.
  * accumulate=0 overwrites grads (first microbatch of a group), 1 adds. */
 int cg_model_backward(cg_model* m, int phase, int layer, int accumulate, void* stream);
+/* the backward of a frozen backbone (loop.py:656-667, freeze_backbone): only the gradients of the aux
+ * parameters -- the termination head from the fused path or d_term_logits, each offset head's two
+ * Linears and biases from d_offset_logits (the head weight is an operand only).  No LM-head dW, no
+ * d(head) product of the offset heads, no dxf product, no ln_f backward, no block weight transposes,
+ * no phase 1 / 2: no element of grads outside the aux parameters' range is written.  accumulate and
+ * the zeroing of unused aux parameters as in phase 0. */
+int cg_model_backward_heads(cg_model* m, int accumulate, void* stream);
 /* pointer to hidden state `which` (0 = embedding output, 1..L = block outputs,
  * L+1 = ln_f output) inside the workspace after a forward; dtype in *dtype_out */
 const void* cg_model_hidden(const cg_model* m, int which, int* dtype_out, long long* ld);
@@ -879,6 +910,57 @@ typedef struct {
 size_t cg_kmeans_workspace(long long n, int d, int k);
 int cg_kmeans_step(const cg_kmeans_desc* k, void* stream);
 
+/* Fused termination-head loss (ABI 0.6 addition): the linear head, its class-weighted cross-entropy and their
+ * backward over the LABELLED rows only.  Replaces termination_head(x) (model_tiny_gpt.py:329-337)
+ * followed by termination_aux_loss (src/codonlm/training/objectives.py:94-105) and their autograd
+ * where the labels are sparse (a replay batch labels at most replay_window positions of a row) or
+ * the logits themselves are not wanted (a frozen-backbone step).
+ *   x [rows][ldx] (x_dtype CG_F32 or CG_BF16, widened exactly; the ln_f output), W fp32 [C][ldw],
+ *   bias fp32 [C], labels device int64 [rows], class_w fp32 [C] or NULL (= 1).
+ *   Row r is LABELLED when labels[r] != ignore_index and 0 <= labels[r] < C.  Any other label --
+ *   ignore_index or out of range -- is ignored (torch would raise a device assert on the latter;
+ *   callers validate their labels on the host).  A row without a label costs its label read and
+ *   nothing else: x is read for labelled rows only.
+ * cg_term_ce_fwd: per labelled row z = x W^T + b (fp32 fma chains: lane l of a wave takes columns
+ *   4 (l + 64 i) .. + 3 in ascending i -- 16-byte loads where ldx, ldw % 4 == 0 and the bases are
+ *   aligned -- and an element tail, then a fixed butterfly), lse = log sum_c exp z_c and
+ *   nll = lse - z_y.  loss (device float, optional) = sum_r w_y nll / sum_r w_y; sums (device
+ *   float[2], optional) = the numerator and the denominator.  Without a labelled row the loss is NaN
+ *   (torch's weighted mean over nothing).  The rows' probabilities and the two sums stay in the
+ *   workspace for the backward.
+ * cg_term_ce_bwd (after cg_term_ce_fwd with the same x, W, bias, labels, class_w and workspace):
+ *   g[r][c] = scale * (scale_dev ? *scale_dev : 1) * w_y (softmax(z_r)_c - [c == y]) / sum_r w_y on
+ *   labelled rows (scale_dev: an optional device float, read in the kernel -- no host sync), and
+ *     dW[c][j] (+)= sum_r g[r][c] x[r][j]   (fp32 [C][lddw], optional)
+ *     db[c]    (+)= sum_r g[r][c]           (fp32 [C], optional)
+ *     dx[r][j] (+)= sum_c g[r][c] W[c][j]   (fp32 [rows][lddx], optional)
+ *   each with its own accumulate flag.  Without acc_dx the unlabelled rows of dx are written as zero;
+ *   with it they are not touched.  Without a labelled row the backward contributes exactly zero.
+ * Reproducible bit for bit: rows are taken in chunks of 64; a chunk's share of a dW / db element is
+ * summed in row order by one thread (fp32), the chunks' shares in chunk order (fp64) by one thread;
+ * the loss sums are fp64 from the per-row fp32 terms in a fixed order.  No floating-point atomics.
+ * The pad columns of x, W, dW and dx are neither read nor written.
+ * rows == 0: CG_OK, nothing touched.  CG_EUNSUPPORTED: C > 16, another x_dtype.  CG_EINVAL: NULL
+ * desc / x / W / bias / labels / workspace, C < 1, d < 1, rows < 0, ldx / ldw / lddw / lddx < d,
+ * ws_bytes below cg_term_ce_workspace(rows, d, C) (workspace 16-byte aligned). */
+typedef struct {
+  int x_dtype; const void* x; long long ldx;
+  long long rows; int d, C;
+  const float* W; long long ldw;
+  const float* bias;
+  const int64_t* labels; int ignore_index;
+  const float* class_w;
+  float* loss; float* sums;                 /* forward outputs */
+  float scale; const float* scale_dev;      /* backward */
+  float* dW; long long lddw; int acc_dW;
+  float* db; int acc_db;
+  float* dx; long long lddx; int acc_dx;
+  void* workspace; size_t ws_bytes;
+} cg_term_ce_desc;
+size_t cg_term_ce_workspace(long long rows, int d, int C);
+int cg_term_ce_fwd(const cg_term_ce_desc* p, void* stream);
+int cg_term_ce_bwd(const cg_term_ce_desc* p, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -915,7 +997,8 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
 /* sizeof the named ABI struct ("cg_gemm_desc", "cg_dw_product", "cg_dw_group", "cg_reduce_job",
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
- * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc", "cg_kmeans_desc"), 0 for
+ * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc", "cg_kmeans_desc",
+ * "cg_term_ce_desc"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -937,7 +1020,10 @@ size_t cg_struct_bytes(const char* name);
  * cg_model_prefill_hist, cg_model_decode_ragged_hist, cg_offset_prior_workspace and
  * cg_offset_prior_add with cg_offset_prior.  ABI 0.6, additions: input attribution -- cg_attr_seed,
  * cg_attr_reduce and cg_model_input_grad with cg_attr_desc.  ABI 0.6, additions: motif mining --
- * cg_window_keep, cg_window_pool, cg_kmeans_step with cg_kmeans_desc, and cg_kmeans_workspace. */
+ * cg_window_keep, cg_window_pool, cg_kmeans_step with cg_kmeans_desc, and cg_kmeans_workspace.
+ * ABI 0.6, additions: termination-head correction -- cg_term_ce_fwd / cg_term_ce_bwd with
+ * cg_term_ce_desc and cg_term_ce_workspace, cg_model_forward_trunk, cg_model_term_loss,
+ * cg_model_backward_heads, and the term_* fields at the end of cg_model. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

@@ -211,6 +211,35 @@ class TermCeDesc(C.Structure):
                 ("dx", vp), ("lddx", i64), ("acc_dx", i32), ("workspace", vp), ("ws_bytes", sz)]
 
 
+NGRAM_MAX_V = 128  # CG_NGRAM_MAX_V: the dense trigram table is V^3 int64
+# cg_diag_rows: the slice order of the CG_DIAG_* enumerators, under the reference's report names
+DIAG_SLICES = ("all", "after_separator", "window_with_chunk_continuation", "window_without_chunk_continuation",
+               "segment_position_0", "segment_position_1_3", "segment_position_4_15", "segment_position_16_63",
+               "segment_position_64_plus", "target_class_special", "target_class_start_codon",
+               "target_class_stop_codon", "target_class_ordinary_codon")
+DIAG_CLS_SPECIAL, DIAG_CLS_START, DIAG_CLS_STOP, DIAG_CLS_ORDINARY = range(4)
+DIAG_MAX_BINS = 32
+
+
+class NgramNllDesc(C.Structure):
+    """cg_ngram_nll_desc: tok_tri, row_sums, row_count and acc are optional (None = not wanted)"""
+    _fields_ = [("x", vp), ("y", vp), ("B", i32), ("T", i32), ("V", i32), ("pad_id", i32),
+                ("reset_mask", C.POINTER(u32)), ("alpha", C.c_double),
+                ("uni", vp), ("bi", vp), ("tri", vp), ("uni_total", vp), ("bi_total", vp), ("tri_total", vp),
+                ("tok_tri", vp), ("row_sums", vp), ("row_count", vp), ("acc", vp),
+                ("workspace", vp), ("ws_bytes", sz)]
+
+
+class DiagDesc(C.Structure):
+    """cg_diag_desc: every output pointer optional (None = not wanted)"""
+    _fields_ = [("logits", vp), ("ldl", i64), ("x", vp), ("y", vp),
+                ("B", i32), ("T", i32), ("V", i32), ("pad_id", i32), ("sep_id", i32),
+                ("row_flag", vp), ("tok_class", vp), ("edges", vp), ("n_bins", i32),
+                ("slices", vp), ("calib", vp), ("brier_acc", vp),
+                ("nll", vp), ("segpos", vp), ("conf", vp), ("row_nll", vp), ("row_count", vp),
+                ("workspace", vp), ("ws_bytes", sz)]
+
+
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {
     "cg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -310,6 +339,12 @@ SIGNATURES = {
     "cg_term_ce_workspace": (sz, [i64, i32, i32]),
     "cg_term_ce_fwd": (i32, [C.POINTER(TermCeDesc), vp]),
     "cg_term_ce_bwd": (i32, [C.POINTER(TermCeDesc), vp]),
+    "cg_ngram_count": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(u32), vp, vp, vp, vp, vp]),
+    "cg_ngram_totals": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
+    "cg_ngram_nll_workspace": (sz, [i32]),
+    "cg_ngram_nll": (i32, [C.POINTER(NgramNllDesc), vp]),
+    "cg_diag_workspace": (sz, [i32]),
+    "cg_diag_rows": (i32, [C.POINTER(DiagDesc), vp]),
     "cg_model_forward_trunk": (i32, [C.POINTER(Model), vp, i32, i32, i32, u32, i32, vp]),
     "cg_model_term_loss": (i32, [C.POINTER(Model), vp, vp, vp, vp]),
     "cg_model_backward_heads": (i32, [C.POINTER(Model), i32, vp]),

@@ -317,5 +317,11 @@ class DeviceBatchLoader:
             a, b = int(self._bounds[k]), int(self._bounds[k + 1])
             yield self.ds.gather(self._order_dev[a:b], self.order[a:b])
 
+    def iter_rows(self):
+        """As iteration, with the dataset row indices of each batch (host int64): (rows, x, y)."""
+        for k in self.shard():
+            a, b = int(self._bounds[k]), int(self._bounds[k + 1])
+            yield (self.order[a:b], *self.ds.gather(self._order_dev[a:b], self.order[a:b]))
+
 
 __all__ = ["DeviceCodonDataset", "DeviceBatchLoader", "bucket_batches", "PAD_ID"]

@@ -972,3 +972,180 @@ def term_ce_bwd(st: TermCE, *, scale=1.0, scale_dev=None, dW=None, db=None, dx=N
             setattr(p, "ld" + name.lower(), _rows2d(t, f"term_ce_bwd: {name}", (torch.float32,)))
     L.check(L.lib.cg_term_ce_bwd(C.byref(p), L.stream_ptr(dev)), "cg_term_ce_bwd")
     return outs["dW"], outs["db"], outs["dx"]
+
+
+class NgramTables:
+    """Device int64 count tables of the segment-aware n-gram baselines (cg_ngram_count) and, after
+    ngram_totals, their row totals.  ``n_bad`` counts positions skipped for a token outside [0, V)."""
+    __slots__ = ("V", "pad_id", "reset_ids", "uni", "bi", "tri", "n_bad", "uni_total", "bi_total", "tri_total")
+
+    def __init__(self, V, device, pad_id=0, reset_ids=()):
+        V = int(V)
+        if V > L.NGRAM_MAX_V:
+            raise ValueError(f"n-gram tables: V = {V} exceeds {L.NGRAM_MAX_V} (CG_EUNSUPPORTED)")
+        if not torch.device(device).type == "cuda":
+            raise RuntimeError("n-gram tables live on the MI355X; codonlm_amd has no CPU path")
+        self.V, self.pad_id, self.reset_ids = V, int(pad_id), tuple(sorted(int(t) for t in reset_ids))
+        self.uni = torch.zeros(V, dtype=torch.int64, device=device)
+        self.bi = torch.zeros(V, V, dtype=torch.int64, device=device)
+        self.tri = torch.zeros(V, V, V, dtype=torch.int64, device=device)
+        self.n_bad = torch.zeros(1, dtype=torch.int64, device=device)
+        self.uni_total = self.bi_total = self.tri_total = None
+
+
+def _xy(x, y, what):
+    L.require_device(x, what)
+    L.require_device(y, what)
+    if x.dim() != 2 or x.shape != y.shape:
+        raise ValueError(f"{what}: x and y are [B][T]")
+    return x.to(torch.int64).contiguous(), y.to(torch.int64).contiguous()
+
+
+def ngram_count(tables: NgramTables, x, y):
+    """cg_ngram_count: add the counted positions of x, y (device int64 [B][T]) to ``tables``
+    (fit_baselines of the reference's eval_ppl_baselines.py).  The totals become stale."""
+    x, y = _xy(x, y, "ngram_count")
+    B, T = x.shape
+    L.check(L.lib.cg_ngram_count(x.data_ptr(), y.data_ptr(), B, T, tables.V, tables.pad_id,
+                                 _id_mask(tables.reset_ids, "reset ids"), tables.uni.data_ptr(), tables.bi.data_ptr(),
+                                 tables.tri.data_ptr(), tables.n_bad.data_ptr(), L.stream_ptr(x.device)),
+            "cg_ngram_count")
+    tables.uni_total = tables.bi_total = tables.tri_total = None
+    return tables
+
+
+def ngram_totals(tables: NgramTables):
+    """cg_ngram_totals: the row totals over the targets 1 .. V-1, once after fitting."""
+    V, dev = tables.V, tables.uni.device
+    tables.uni_total = torch.empty(1, dtype=torch.int64, device=dev)
+    tables.bi_total = torch.empty(V, dtype=torch.int64, device=dev)
+    tables.tri_total = torch.empty(V, V, dtype=torch.int64, device=dev)
+    L.check(L.lib.cg_ngram_totals(tables.uni.data_ptr(), tables.bi.data_ptr(), tables.tri.data_ptr(), V,
+                                  tables.uni_total.data_ptr(), tables.bi_total.data_ptr(),
+                                  tables.tri_total.data_ptr(), L.stream_ptr(dev)), "cg_ngram_totals")
+    return tables
+
+
+class NgramNll:
+    """Device tensors of one ngram_nll call; an output that was not asked for is None."""
+    __slots__ = ("tok_tri", "row_sums", "row_count", "acc")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
+NGRAM_OUTPUTS = ("tok_tri", "row_sums", "row_count")
+
+
+def ngram_nll(tables: NgramTables, x, y, alpha=0.01, *, acc=None, want=("row_sums", "row_count"), workspace=None):
+    """cg_ngram_nll of x, y (device int64 [B][T]) under ``tables`` (evaluate_baselines / _trigram_nll of
+    the reference): ``tok_tri`` fp32 [B][T], ``row_sums`` fp64 [B][4] (uniform, unigram, bigram,
+    trigram), ``row_count`` int32 [B], and ``acc``: the fp64 [5] accumulator the launch added to."""
+    x, y = _xy(x, y, "ngram_nll")
+    unknown = set(want) - set(NGRAM_OUTPUTS)
+    if unknown:
+        raise ValueError(f"ngram_nll: unknown outputs {sorted(unknown)}")
+    if tables.uni_total is None:
+        raise ValueError("ngram_nll: call ngram_totals after the last ngram_count")
+    B, T = x.shape
+    dev = x.device
+    d = L.NgramNllDesc()
+    d.x, d.y, d.B, d.T, d.V, d.pad_id = x.data_ptr(), y.data_ptr(), B, T, tables.V, tables.pad_id
+    d.reset_mask = _id_mask(tables.reset_ids, "reset ids")
+    d.alpha = float(alpha)
+    for name in ("uni", "bi", "tri", "uni_total", "bi_total", "tri_total"):
+        setattr(d, name, getattr(tables, name).data_ptr())
+    res = NgramNll()
+    for name, shape, dt in (("tok_tri", (B, T), torch.float32), ("row_sums", (B, 4), torch.float64),
+                            ("row_count", (B,), torch.int32)):
+        if name in want:
+            t = torch.empty(shape, dtype=dt, device=dev)
+            setattr(res, name, t)
+            setattr(d, name, t.data_ptr())
+    if acc is not None:
+        if acc.dtype != torch.float64 or acc.numel() != 5 or not acc.is_cuda or not acc.is_contiguous():
+            raise ValueError("ngram_nll: acc is a contiguous device fp64 [5]")
+        res.acc = acc
+        d.acc = acc.data_ptr()
+        ws = workspace if workspace is not None else torch.empty(
+            int(L.lib.cg_ngram_nll_workspace(B)) // 8 + 1, dtype=torch.float64, device=dev)
+        d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    L.check(L.lib.cg_ngram_nll(C.byref(d), L.stream_ptr(dev)), "cg_ngram_nll")
+    return res
+
+
+class DiagResult:
+    """Device tensors of one diag_rows call; an output that was not asked for is None."""
+    __slots__ = ("nll", "segpos", "conf", "row_nll", "row_count", "slices", "calib", "brier_acc")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
+DIAG_OUTPUTS = ("nll", "segpos", "conf", "row_nll", "row_count")
+
+
+def diag_workspace(B, device):
+    """A cg_diag_rows workspace for up to ``B`` rows (8-byte aligned)."""
+    return torch.empty(int(L.lib.cg_diag_workspace(int(B))) // 8 + 1, dtype=torch.float64, device=device)
+
+
+def _dev_tensor(t, dtype, numel, what):
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{what} is a contiguous device {dtype} of {numel} elements")
+    return t.data_ptr()
+
+
+def diag_rows(logits, x, y, *, V=None, pad_id=0, sep_id=3, row_flag=None, tok_class=None, edges=None, slices=None,
+              calib=None, brier_acc=None, want=(), workspace=None):
+    """cg_diag_rows over the fp32 logits [B*T][ld] of a forward over x with the targets y (device int64
+    [B][T]): the loss slices, calibration bins and Brier sums the reference's diagnose_context_learning.py
+    and calibration_metrics.py take in Python loops.  ``slices`` fp64 [13][2], ``calib`` fp64
+    [n_bins][3] (with ``edges`` fp32 [n_bins + 1]) and ``brier_acc`` fp64 [2] are device accumulators
+    the launch adds to; ``want`` names per-token (nll, segpos, conf: [B][T]) and per-row (row_nll fp64,
+    row_count int32: [B]) outputs."""
+    L.require_device(logits, "diag_rows")
+    x, y = _xy(x, y, "diag_rows")
+    B, T = x.shape
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] != B * T or \
+            (logits.shape[0] and logits.stride(1) != 1):
+        raise ValueError("diag_rows: logits is fp32 [B*T][ld] with contiguous rows")
+    unknown = set(want) - set(DIAG_OUTPUTS)
+    if unknown:
+        raise ValueError(f"diag_rows: unknown outputs {sorted(unknown)}")
+    V = logits.shape[1] if V is None else int(V)
+    dev = logits.device
+    d = L.DiagDesc()
+    d.logits, d.ldl = logits.data_ptr(), logits.stride(0) if B * T else V
+    d.x, d.y, d.B, d.T, d.V, d.pad_id, d.sep_id = x.data_ptr(), y.data_ptr(), B, T, V, int(pad_id), int(sep_id)
+    if row_flag is not None:
+        d.row_flag = _dev_tensor(row_flag, torch.uint8, B, "diag_rows: row_flag")
+    if tok_class is not None:
+        d.tok_class = _dev_tensor(tok_class, torch.uint8, V, "diag_rows: tok_class")
+    res = DiagResult()
+    if edges is not None:
+        n_bins = edges.numel() - 1
+        d.edges, d.n_bins = _dev_tensor(edges, torch.float32, n_bins + 1, "diag_rows: edges"), n_bins
+        if calib is not None:
+            d.calib = _dev_tensor(calib, torch.float64, 3 * n_bins, "diag_rows: calib")
+    elif calib is not None:
+        raise ValueError("diag_rows: calib needs edges")
+    if slices is not None:
+        d.slices = _dev_tensor(slices, torch.float64, 2 * len(L.DIAG_SLICES), "diag_rows: slices")
+    if brier_acc is not None:
+        d.brier_acc = _dev_tensor(brier_acc, torch.float64, 2, "diag_rows: brier_acc")
+    res.slices, res.calib, res.brier_acc = slices, calib, brier_acc
+    for name, shape, dt in (("nll", (B, T), torch.float32), ("segpos", (B, T), torch.int32),
+                            ("conf", (B, T), torch.float32), ("row_nll", (B,), torch.float64),
+                            ("row_count", (B,), torch.int32)):
+        if name in want:
+            t = torch.empty(shape, dtype=dt, device=dev)
+            setattr(res, name, t)
+            setattr(d, name, t.data_ptr())
+    if slices is not None or calib is not None or brier_acc is not None:
+        ws = workspace if workspace is not None else diag_workspace(B, dev)
+        d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    L.check(L.lib.cg_diag_rows(C.byref(d), L.stream_ptr(dev)), "cg_diag_rows")
+    return res

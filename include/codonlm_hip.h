@@ -961,6 +961,112 @@ size_t cg_term_ce_workspace(long long rows, int d, int C);
 int cg_term_ce_fwd(const cg_term_ce_desc* p, void* stream);
 int cg_term_ce_bwd(const cg_term_ce_desc* p, void* stream);
 
+/* Context diagnostic (ABI 0.6 addition): segment-aware n-gram baselines and the sliced loss /
+ * calibration pass of the reference's leakage-controlled revalidation scripts, each of which is a
+ * Python loop per token there.  Shared conventions: x, y are device int64 [B][T] (inputs and
+ * next-token targets, as the engine takes them); V <= CG_NGRAM_MAX_V = 128, else CG_EUNSUPPORTED
+ * (the dense trigram table is V^3 int64); pad_id (0 <= pad_id < V, the reference's is 0) is the
+ * ignored target; reset_mask is cg_window_keep's id mask (host, 8 x 32-bit words = ids 0..255): the
+ * tokens after which the n-gram history restarts (<SEP>).  All row arithmetic is fp64 and an fp32
+ * output is the single rounding of the fp64 value.  No floating-point atomics: per-workgroup fp64
+ * partials go to the workspace and one single-workgroup launch adds them in a fixed order, so the same
+ * inputs give the same bits; the integer tables use integer atomics, which are order-independent.
+ * B == 0 or T == 0: CG_OK, nothing touched.  CG_EINVAL: a NULL required pointer, a negative size,
+ * pad_id outside [0, V), a misaligned (8 bytes) or short workspace.
+ *
+ * cg_ngram_count (fit_baselines, scripts/eval_ppl_baselines.py:61-84): position (b, t) counts when
+ * y != pad_id.  previous = x[b][t]; previous2 = pad_id when t == 0 or previous is a reset token,
+ * else x[b][t-1].  A counted position whose y, previous or (read) previous2 lies outside [0, V)
+ * adds 1 to n_bad[0] (optional) and is skipped; any other adds 1 to uni[y], bi[previous][y] and
+ * tri[previous2][previous][y].  uni [V], bi [V][V], tri [V][V][V] are device int64 and += across
+ * launches (the caller zeroes them).  Bigram counts are taken in a per-workgroup 32-bit LDS table and
+ * its non-zero cells flushed with 64-bit global integer adds (the unigram counts are that table's
+ * column sums); trigram adds go straight to global memory without a returned value.  More than
+ * 2^40 positions in one launch: CG_EUNSUPPORTED.
+ *
+ * cg_ngram_totals (_probability, :87-90): uni_total[0], bi_total[p] and tri_total[p2][p] = the sum
+ * of the row's counts over the targets 1 .. V-1 (the reference leaves column 0 out), device int64
+ * [1], [V], [V][V]; overwritten. */
+#define CG_NGRAM_MAX_V 128
+int cg_ngram_count(const int64_t* x, const int64_t* y, int B, int T, int V, int pad_id, const uint32_t* reset_mask,
+                   long long* uni, long long* bi, long long* tri, long long* n_bad, void* stream);
+int cg_ngram_totals(const long long* uni, const long long* bi, const long long* tri, int V, long long* uni_total,
+                    long long* bi_total, long long* tri_total, void* stream);
+/* cg_ngram_nll (evaluate_baselines, scripts/eval_ppl_baselines.py:93-137, and _trigram_nll,
+ * scripts/diagnose_context_learning.py:78-105): with active = V - 1,
+ *   p = (count + alpha) / (total + alpha * active), nll = -log p
+ * for the unigram row, the bigram row of previous, and the trigram row of (previous2, previous) when
+ * its total is non-zero, else the bigram row of previous (the reference's trigram.get(...) is None
+ * back-off: with pad_id = 0 column 0 is never counted, so a context exists exactly when its total is
+ * non-zero).  An unseen context gives alpha / (alpha * active); the uniform model gives log(active).
+ * A position counts as in cg_ngram_count; one with a token outside [0, V) is skipped.
+ * Outputs, all optional:
+ *   tok_tri   fp32 [B][T]: the trigram nll, 0 where not counted;
+ *   row_sums  fp64 [B][4]: the row's uniform, unigram, bigram and trigram nll sums (lane t % 64 of one
+ *             wave adds position t in order, a fixed butterfly follows), row_count int32 [B];
+ *   acc       fp64 [5], += across launches: the four sums and the number of counted positions.
+ * workspace: cg_ngram_nll_workspace(B) bytes.  alpha <= 0 (or not finite): CG_EINVAL. */
+typedef struct {
+  const int64_t* x; const int64_t* y;
+  int B, T, V, pad_id;
+  const uint32_t* reset_mask;
+  double alpha;
+  const long long* uni; const long long* bi; const long long* tri;
+  const long long* uni_total; const long long* bi_total; const long long* tri_total;
+  float* tok_tri;
+  double* row_sums; int32_t* row_count;
+  double* acc;
+  void* workspace; size_t ws_bytes;
+} cg_ngram_nll_desc;
+size_t cg_ngram_nll_workspace(int B);
+int cg_ngram_nll(const cg_ngram_nll_desc* d, void* stream);
+/* cg_diag_rows: one pass over the fp32 logits [B*T][ldl] (the first V columns are read) of a forward
+ * over x with the targets y.  It replaces the slice loop of scripts/diagnose_context_learning.py
+ * :322-357 and ece_from_logits / brier_from_logits of scripts/calibration_metrics.py:35-75.
+ * Position (b, t) is VALID when y != pad_id and 0 <= y < V.  Per valid position, in fp64:
+ *   lse = log sum_c exp z_c, nll = lse - z_y, conf = exp(zmax - lse) = 1 / sum_c exp(z_c - zmax),
+ *   correct = (the lowest-index argmax == y), brier = sum_c p_c^2 - 2 p_y + 1.
+ * Segment position (the reference's counter): it runs over the valid positions of a row from 0, is
+ * set to 0 at a valid position whose input is sep_id, and grows by 1 after each valid position; an
+ * invalid position neither resets nor advances it, even when its input is the separator.  One
+ * workgroup per row scans it, for any T.
+ * slices fp64 [CG_DIAG_SLICES][2] = (sum of nll, count), += across launches, in the order of the
+ * CG_DIAG_* enumerators: all; after_separator (valid and x == sep_id); row_flag set, row_flag clear
+ * (row_flag device uint8 [B], NULL = clear: the chunk-continuation windows); the segment-position
+ * bins 0, 1-3, 4-15, 16-63, 64+; the four target classes of tok_class (device uint8 [V] of
+ * CG_DIAG_CLS_*, NULL = no class slices; a value above 3 joins none).
+ * Calibration: edges device fp32 [n_bins + 1], 1 <= n_bins <= CG_DIAG_MAX_BINS; conf rounded to fp32
+ * falls in bin i when conf > edges[i] && conf <= edges[i+1] (the lowest such i; none: not binned).
+ * calib fp64 [n_bins][3] = (count, sum of conf, sum of correct), brier_acc fp64 [2] = (sum, count),
+ * both += across launches.  edges NULL: no calibration (calib must be NULL too).
+ * Optional per-token outputs [B][T]: nll fp32 (0 where invalid), segpos int32 (-1 where invalid),
+ * conf fp32 (0 where invalid).  Optional per-row outputs: row_nll fp64 [B] and row_count int32 [B],
+ * summed as cg_score_rows sums seq_logp (lane t % 64 of one wave adds position t in order, a fixed
+ * butterfly follows; invalid positions add exactly 0).
+ * workspace: cg_diag_workspace(B) bytes (needed with slices, calib or brier_acc). */
+enum {
+  CG_DIAG_ALL = 0, CG_DIAG_AFTER_SEP = 1, CG_DIAG_FLAG_SET = 2, CG_DIAG_FLAG_CLEAR = 3,
+  CG_DIAG_POS_0 = 4, CG_DIAG_POS_1_3 = 5, CG_DIAG_POS_4_15 = 6, CG_DIAG_POS_16_63 = 7, CG_DIAG_POS_64_PLUS = 8,
+  CG_DIAG_CLS_SPECIAL_SLICE = 9, CG_DIAG_CLS_START_SLICE = 10, CG_DIAG_CLS_STOP_SLICE = 11,
+  CG_DIAG_CLS_ORDINARY_SLICE = 12, CG_DIAG_SLICES = 13
+};
+enum { CG_DIAG_CLS_SPECIAL = 0, CG_DIAG_CLS_START = 1, CG_DIAG_CLS_STOP = 2, CG_DIAG_CLS_ORDINARY = 3 };
+#define CG_DIAG_MAX_BINS 32
+typedef struct {
+  const float* logits; long long ldl;
+  const int64_t* x; const int64_t* y;
+  int B, T, V, pad_id, sep_id;
+  const uint8_t* row_flag;
+  const uint8_t* tok_class;
+  const float* edges; int n_bins;
+  double* slices; double* calib; double* brier_acc;
+  float* nll; int32_t* segpos; float* conf;
+  double* row_nll; int32_t* row_count;
+  void* workspace; size_t ws_bytes;
+} cg_diag_desc;
+size_t cg_diag_workspace(int B);
+int cg_diag_rows(const cg_diag_desc* d, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -998,7 +1104,7 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
  * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc", "cg_kmeans_desc",
- * "cg_term_ce_desc"), 0 for
+ * "cg_term_ce_desc", "cg_ngram_nll_desc", "cg_diag_desc"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -1023,7 +1129,9 @@ size_t cg_struct_bytes(const char* name);
  * cg_window_keep, cg_window_pool, cg_kmeans_step with cg_kmeans_desc, and cg_kmeans_workspace.
  * ABI 0.6, additions: termination-head correction -- cg_term_ce_fwd / cg_term_ce_bwd with
  * cg_term_ce_desc and cg_term_ce_workspace, cg_model_forward_trunk, cg_model_term_loss,
- * cg_model_backward_heads, and the term_* fields at the end of cg_model. */
+ * cg_model_backward_heads, and the term_* fields at the end of cg_model.  ABI 0.6, additions: context
+ * diagnostic -- cg_ngram_count, cg_ngram_totals, cg_ngram_nll with cg_ngram_nll_desc and
+ * cg_ngram_nll_workspace, cg_diag_rows with cg_diag_desc and cg_diag_workspace. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

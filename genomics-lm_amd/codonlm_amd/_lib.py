@@ -240,6 +240,23 @@ class DiagDesc(C.Structure):
                 ("workspace", vp), ("ws_bytes", sz)]
 
 
+# cg_attn_stats: the statistic order of the CG_AS_* enumerators
+AS_STATS = ("entropy", "norm_entropy", "mass_special", "mass_start", "mass_stop", "mass_ordinary",
+            "dist_0", "dist_1_3", "dist_4_15", "dist_16_63", "dist_64_plus", "mean_dist", "max_prob", "first")
+(AS_ENTROPY, AS_NORM_ENTROPY, AS_MASS_SPECIAL, AS_MASS_START, AS_MASS_STOP, AS_MASS_ORDINARY, AS_DIST_0, AS_DIST_1_3,
+ AS_DIST_4_15, AS_DIST_16_63, AS_DIST_64_PLUS, AS_MEAN_DIST, AS_MAX_PROB, AS_FIRST) = range(14)
+AS_NSTAT = 14
+
+
+class AttnStatsDesc(C.Structure):
+    """cg_attn_stats_desc: every output pointer optional (None = not wanted)"""
+    _fields_ = [("dtype", i32), ("qkv", vp), ("ldqkv", i64), ("segstart", vp),
+                ("B", i32), ("T", i32), ("H", i32), ("KV", i32), ("hd", i32), ("window", i32),
+                ("idx", vp), ("pad_id", i32), ("tok_class", vp), ("V", i32), ("row_keep", vp),
+                ("rows", vp), ("nvis", vp), ("received", vp), ("head_acc", vp), ("n_rows", vp),
+                ("workspace", vp), ("ws_bytes", sz)]
+
+
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {
     "cg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -345,6 +362,9 @@ SIGNATURES = {
     "cg_ngram_nll": (i32, [C.POINTER(NgramNllDesc), vp]),
     "cg_diag_workspace": (sz, [i32]),
     "cg_diag_rows": (i32, [C.POINTER(DiagDesc), vp]),
+    "cg_attn_stats_workspace": (sz, [i32, i32, i32]),
+    "cg_attn_stats": (i32, [C.POINTER(AttnStatsDesc), vp]),
+    "cg_model_attn_stats": (i32, [C.POINTER(Model), i32, C.POINTER(AttnStatsDesc), vp]),
     "cg_model_forward_trunk": (i32, [C.POINTER(Model), vp, i32, i32, i32, u32, i32, vp]),
     "cg_model_term_loss": (i32, [C.POINTER(Model), vp, vp, vp, vp]),
     "cg_model_backward_heads": (i32, [C.POINTER(Model), i32, vp]),

@@ -422,6 +422,25 @@ class Engine:
                 "cg_model_attn_probs")
         return out
 
+    def attn_stats(self, layer: int, *, pad_id: int = -1, tok_class=None, row_keep=None,
+                   want=("rows", "nvis", "received"), head_acc=None, n_rows=None, workspace=None):
+        """cg_attn_stats on block `layer` of the last forward (any forward; nothing T x T is written):
+        an ops.AttnStatsResult.  The layer's qkv rows, SEP mask, window and token ids are the
+        forward's; the keywords are those of ops.attn_stats."""
+        from . import ops
+        B, T, H = self.model.B, self.model.T, self.cfg.n_head
+        if getattr(self, "_idx", None) is None or B <= 0:
+            raise ValueError("attn_stats: run a forward first")
+        dev = self.flat.device
+        d = L.AttnStatsDesc()
+        res = ops.AttnStatsResult()
+        keep = ops.attn_stats_fill(d, res, B, T, H, dev, pad_id=pad_id, tok_class=tok_class, row_keep=row_keep,
+                                   want=want, head_acc=head_acc, n_rows=n_rows, workspace=workspace)
+        L.check(L.lib.cg_model_attn_stats(C.byref(self.model), int(layer), C.byref(d), L.stream_ptr(dev)),
+                "cg_model_attn_stats")
+        del keep
+        return res
+
     def hidden(self, which: int) -> torch.Tensor:
         dt = C.c_int(0)
         ld = C.c_longlong(0)

@@ -1149,3 +1149,81 @@ def diag_rows(logits, x, y, *, V=None, pad_id=0, sep_id=3, row_flag=None, tok_cl
         d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     L.check(L.lib.cg_diag_rows(C.byref(d), L.stream_ptr(dev)), "cg_diag_rows")
     return res
+
+
+class AttnStatsResult:
+    """Device tensors of one attn_stats call; an output that was not asked for is None."""
+    __slots__ = ("rows", "nvis", "received", "head_acc", "n_rows")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
+ATTN_STATS_OUTPUTS = ("rows", "nvis", "received")
+
+
+def attn_stats_workspace(B, T, H, device):
+    """A cg_attn_stats workspace for (B, T, H) (8-byte aligned)."""
+    return torch.empty(int(L.lib.cg_attn_stats_workspace(int(B), int(T), int(H))) // 8 + 1, dtype=torch.float64,
+                       device=device)
+
+
+def attn_stats_fill(d, res, B, T, H, dev, *, idx=None, pad_id=-1, tok_class=None, row_keep=None,
+                    want=ATTN_STATS_OUTPUTS, head_acc=None, n_rows=None, workspace=None):
+    """The fields of an AttnStatsDesc a caller chooses (token ids, classes, row filter, outputs,
+    workspace), shared by attn_stats and Engine.attn_stats; returns the tensors to keep alive."""
+    unknown = set(want) - set(ATTN_STATS_OUTPUTS)
+    if unknown:
+        raise ValueError(f"attn_stats: unknown outputs {sorted(unknown)}")
+    keep = []
+    if idx is not None:
+        idx = idx.to(device=dev, dtype=torch.int64).contiguous()
+        d.idx = _dev_tensor(idx, torch.int64, B * T, "attn_stats: idx")
+        keep.append(idx)
+    d.pad_id = int(pad_id)
+    if tok_class is not None:
+        d.tok_class, d.V = _dev_tensor(tok_class, torch.uint8, tok_class.numel(), "attn_stats: tok_class"), tok_class.numel()
+    if row_keep is not None:
+        row_keep = row_keep.to(device=dev, dtype=torch.uint8).contiguous()
+        d.row_keep = _dev_tensor(row_keep, torch.uint8, B * T, "attn_stats: row_keep")
+        keep.append(row_keep)
+    for name, shape, dt in (("rows", (B, H, T, L.AS_NSTAT), torch.float32), ("nvis", (B, T), torch.int32),
+                            ("received", (B, H, T), torch.float32)):
+        if name in want:
+            t = torch.empty(shape, dtype=dt, device=dev)
+            setattr(res, name, t)
+            setattr(d, name, t.data_ptr())
+    if head_acc is not None:
+        d.head_acc = _dev_tensor(head_acc, torch.float64, H * L.AS_NSTAT, "attn_stats: head_acc")
+    if n_rows is not None:
+        d.n_rows = _dev_tensor(n_rows, torch.float64, 1, "attn_stats: n_rows")
+    res.head_acc, res.n_rows = head_acc, n_rows
+    ws = workspace if workspace is not None else attn_stats_workspace(B, T, H, dev)
+    d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    keep.append(ws)
+    return keep
+
+
+def attn_stats(qkv, segstart, B, T, H, KV, hd, *, window=0, idx=None, pad_id=-1, tok_class=None, row_keep=None,
+               want=ATTN_STATS_OUTPUTS, head_acc=None, n_rows=None, workspace=None):
+    """cg_attn_stats over the qkv rows [B*T][(H + 2 KV) hd] of a forward (RoPE applied): the per-row
+    statistics of the attention probabilities (``rows`` fp32 [B][H][T][14] in the order of
+    L.AS_STATS), ``nvis`` int32 [B][T], ``received`` fp32 [B][H][T], and the device accumulators
+    ``head_acc`` fp64 [H][14] and ``n_rows`` fp64 [1] the launch adds to.  No T x T tensor is
+    written.  ``idx`` int64 [B][T] with ``pad_id`` drops PAD rows and, with ``tok_class`` uint8 [V],
+    gives the key classes; ``row_keep`` uint8 [B][T] filters the query rows."""
+    L.require_device(qkv, "attn_stats")
+    if qkv.dim() != 2 or qkv.shape[0] != B * T or (qkv.numel() and qkv.stride(1) != 1):
+        raise ValueError("attn_stats: qkv is [B*T][(H + 2 KV) hd] with contiguous rows")
+    dev = qkv.device
+    d = L.AttnStatsDesc()
+    d.dtype, d.qkv, d.ldqkv = _dt(qkv), qkv.data_ptr(), qkv.stride(0) if qkv.numel() else (H + 2 * KV) * hd
+    d.segstart = _p(segstart)
+    d.B, d.T, d.H, d.KV, d.hd, d.window = B, T, H, KV, hd, int(window or 0)
+    res = AttnStatsResult()
+    keep = attn_stats_fill(d, res, B, T, H, dev, idx=idx, pad_id=pad_id, tok_class=tok_class, row_keep=row_keep,
+                           want=want, head_acc=head_acc, n_rows=n_rows, workspace=workspace)
+    L.check(L.lib.cg_attn_stats(C.byref(d), L.stream_ptr(dev)), "cg_attn_stats")
+    del keep
+    return res

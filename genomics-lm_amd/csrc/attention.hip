@@ -14,6 +14,7 @@
 //                    bf16 fallback for head dims the MFMA kernel does not cover.
 //   * attn_*_mfma  : bf16 MFMA 32x32x16 kernels (hd in {32, 48, 64}) -- attention_mfma.h
 //   * attn_fwd_f32mfma : the fp32 forward on f32 MFMA (hd % 8 == 0, hd <= 64) -- attention_f32.h
+// Per-head statistics of P without the T x T tensor (cg_attn_stats) -- attention_stats.h
 #include "common.h"
 
 constexpr int AV_HD = 64;   // max head dim of the vector kernels
@@ -284,6 +285,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dkdv_vec(const T* __restrict__ qk
 
 #include "attention_mfma.h"
 #include "attention_f32.h"
+#include "attention_stats.h"
 
 // ---------------------------------------------------------------------------
 // Attention probabilities of one layer, materialised (the manual path's `last_attn`,

@@ -1477,6 +1477,24 @@ extern "C" int cg_model_attn_probs(const cg_model* m, int layer, float* out, voi
                        C.D.KV, C.D.hd, m->window, C.s);
 }
 
+// per-head attention statistics of block `layer` of the last forward (cg_attn_stats): the layer's
+// qkv rows, mask and tokens from the model, the class table, row filter and outputs from d
+extern "C" int cg_model_attn_stats(const cg_model* m, int layer, const cg_attn_stats_desc* d, void* stream) {
+  if (!m || !d || !m->idx || m->B <= 0 || m->T <= 0) return CG_EINVAL;
+  Ctx C;
+  CK(make_ctx(m, m->B, m->T, stream, C));
+  if (layer < 0 || layer >= C.D.L) return CG_EINVAL;
+  cg_attn_stats_desc a = *d;
+  a.dtype = C.dt;
+  a.qkv = C.A.la[layer].qkv;
+  a.ldqkv = C.D.Nqkv;
+  a.segstart = m->cfg.sep_id >= 0 ? C.A.seg : nullptr;
+  a.B = C.B; a.T = C.T; a.H = C.D.H; a.KV = C.D.KV; a.hd = C.D.hd;
+  a.window = m->window;
+  a.idx = m->idx;
+  return cg_attn_stats(&a, C.s);
+}
+
 extern "C" const void* cg_model_hidden(const cg_model* m, int which, int* dtype_out, long long* ld) {
   if (!m) return nullptr;
   Ctx C;
@@ -1845,6 +1863,7 @@ extern "C" size_t cg_struct_bytes(const char* name) {
   CG_SZ(cg_param_entry) CG_SZ(cg_model) CG_SZ(cg_model_opts) CG_SZ(cg_sample_params) CG_SZ(cg_gen_state)
   CG_SZ(cg_score_desc) CG_SZ(cg_sample_plan) CG_SZ(cg_offset_prior) CG_SZ(cg_attr_desc)
   CG_SZ(cg_kmeans_desc) CG_SZ(cg_term_ce_desc) CG_SZ(cg_ngram_nll_desc) CG_SZ(cg_diag_desc)
+  CG_SZ(cg_attn_stats_desc)
 #undef CG_SZ
   return 0;
 }

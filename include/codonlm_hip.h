@@ -1067,6 +1067,58 @@ typedef struct {
 size_t cg_diag_workspace(int B);
 int cg_diag_rows(const cg_diag_desc* d, void* stream);
 
+/* cg_attn_stats: per-head statistics of the attention probabilities P of one layer, over any number
+ * of sequences, without a T x T tensor reaching memory.  It replaces the per-head reductions of
+ * scripts/conference_attention.py:41-66 (_head_stats: entropy, start- and stop-column bias) and the
+ * row reductions scripts/analyze_attention.py and scripts/report_top_saliency.py take from the
+ * captured `attn` tensor of collect_artifacts_yaml.py, which cg_attn_probs could only serve by
+ * writing B*H*T*T floats per layer.
+ * qkv as cg_attn_fwd (rows [B*T], q | k | v, RoPE already applied).  Key k is visible to query q iff
+ * lo(q) <= k <= q, lo = max(segstart[b,q], q - window + 1) (the forward's mask); query head h reads
+ * KV head h / (H/KV); scale 1/sqrt(hd).  The op is self-normalised: it takes each row's maximum and
+ * normaliser itself in fp32 (pass A over the row's key tiles) and adds p = exp(s - lse) into every
+ * sum in fp32 (pass B), for bf16 inputs too; the forward's saved LSE is not read.
+ * A row (b, q) is KEPT iff (idx == NULL or idx[b,q] != pad_id) and (row_keep == NULL or
+ * row_keep[b,q] != 0).  The class of key k is tok_class[idx[b,k]]; a class above 3 or a token
+ * outside [0, V) joins no class; tok_class without idx is CG_EINVAL.
+ * Outputs, all optional: rows (0 on rows not kept), nvis (every row), received[b][h][k] = the sum
+ * over the kept queries q of p[q][k], head_acc[h][s] += the fp64 sum over the kept rows of the fp32
+ * row statistics, n_rows += the kept (b, q) count.  Every sum has a fixed order (per 128-query tile
+ * in query order, then the tiles in ascending order): two runs give identical bits, no atomics.
+ * bf16 with hd % 8 == 0 runs on v_mfma_f32_32x32x16_bf16 with the forward's K-tile DMA; fp32 and
+ * other head dims on a vector kernel.  hd in 1..64 (more: CG_EUNSUPPORTED).  B == 0 or T == 0:
+ * CG_OK, nothing written.  CG_EINVAL: H % KV != 0, a NULL qkv, ldqkv below (H + 2 KV) hd, a workspace
+ * (always needed, 8-byte aligned) smaller than cg_attn_stats_workspace(B, T, H). */
+enum { CG_AS_ENTROPY = 0,            /* -sum p ln p over the visible keys, nats            */
+       CG_AS_NORM_ENTROPY = 1,       /* entropy / ln(nvis); 0 when nvis == 1                */
+       CG_AS_MASS_SPECIAL = 2, CG_AS_MASS_START = 3, CG_AS_MASS_STOP = 4, CG_AS_MASS_ORDINARY = 5,
+                                     /* sum of p over keys of class CG_DIAG_CLS_* (same order) */
+       CG_AS_DIST_0 = 6, CG_AS_DIST_1_3 = 7, CG_AS_DIST_4_15 = 8, CG_AS_DIST_16_63 = 9, CG_AS_DIST_64_PLUS = 10,
+                                     /* sum of p over keys at distance q - k in the bin      */
+       CG_AS_MEAN_DIST = 11,         /* sum p (q - k)                                        */
+       CG_AS_MAX_PROB = 12,          /* max p                                                */
+       CG_AS_FIRST = 13,             /* p at the first visible key lo(q) (the "sink")        */
+       CG_AS_NSTAT = 14 };
+typedef struct {
+  int dtype; const void* qkv; long long ldqkv;          /* as cg_attn_fwd: rows [B*T], q | k | v, RoPE already applied */
+  const int32_t* segstart;                              /* NULL = no SEP mask */
+  int B, T, H, KV, hd, window;
+  const int64_t* idx; int pad_id;                       /* idx NULL = every row kept, no classes */
+  const uint8_t* tok_class; int V;                      /* uint8 [V] of CG_DIAG_CLS_*; NULL = class masses are 0 */
+  const uint8_t* row_keep;                              /* uint8 [B][T], NULL = all */
+  float* rows;                                          /* optional fp32 [B][H][T][CG_AS_NSTAT], 0 on rows not kept */
+  int32_t* nvis;                                        /* optional int32 [B][T] = q - lo(q) + 1 */
+  float* received;                                      /* optional fp32 [B][H][T]: sum over kept queries q of p[q][k] */
+  double* head_acc;                                     /* optional fp64 [H][CG_AS_NSTAT], += across launches */
+  double* n_rows;                                       /* optional fp64 [1], += the kept (b, q) count */
+  void* workspace; size_t ws_bytes;
+} cg_attn_stats_desc;
+size_t cg_attn_stats_workspace(int B, int T, int H);
+int cg_attn_stats(const cg_attn_stats_desc* d, void* stream);
+/* cg_attn_stats on block `layer` of the last forward: dtype, qkv, ldqkv, segstart, B, T, H, KV, hd,
+ * window and idx come from the model (as cg_model_attn_probs takes them), every other field from d */
+int cg_model_attn_stats(const cg_model* m, int layer, const cg_attn_stats_desc* d, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -1104,7 +1156,7 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
  * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc", "cg_kmeans_desc",
- * "cg_term_ce_desc", "cg_ngram_nll_desc", "cg_diag_desc"), 0 for
+ * "cg_term_ce_desc", "cg_ngram_nll_desc", "cg_diag_desc", "cg_attn_stats_desc"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -1131,7 +1183,9 @@ size_t cg_struct_bytes(const char* name);
  * cg_term_ce_desc and cg_term_ce_workspace, cg_model_forward_trunk, cg_model_term_loss,
  * cg_model_backward_heads, and the term_* fields at the end of cg_model.  ABI 0.6, additions: context
  * diagnostic -- cg_ngram_count, cg_ngram_totals, cg_ngram_nll with cg_ngram_nll_desc and
- * cg_ngram_nll_workspace, cg_diag_rows with cg_diag_desc and cg_diag_workspace. */
+ * cg_ngram_nll_workspace, cg_diag_rows with cg_diag_desc and cg_diag_workspace.  ABI 0.6, additions:
+ * attention head analysis -- cg_attn_stats with cg_attn_stats_desc, cg_attn_stats_workspace and
+ * cg_model_attn_stats. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

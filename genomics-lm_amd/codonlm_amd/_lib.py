@@ -365,6 +365,9 @@ SIGNATURES = {
     "cg_attn_stats_workspace": (sz, [i32, i32, i32]),
     "cg_attn_stats": (i32, [C.POINTER(AttnStatsDesc), vp]),
     "cg_model_attn_stats": (i32, [C.POINTER(Model), i32, C.POINTER(AttnStatsDesc), vp]),
+    "cg_shape_targets": (i32, [vp, i32, i32, C.POINTER(i32), i32, vp, i64, vp, vp]),
+    "cg_gram_workspace": (sz, [i64, i32, i32, i32]),
+    "cg_gram_accum": (i32, [i32, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, vp, i64, vp, sz, vp]),
     "cg_model_forward_trunk": (i32, [C.POINTER(Model), vp, i32, i32, i32, u32, i32, vp]),
     "cg_model_term_loss": (i32, [C.POINTER(Model), vp, vp, vp, vp]),
     "cg_model_backward_heads": (i32, [C.POINTER(Model), i32, vp]),

@@ -1227,3 +1227,102 @@ def attn_stats(qkv, segstart, B, T, H, KV, hd, *, window=0, idx=None, pad_id=-1,
     L.check(L.lib.cg_attn_stats(C.byref(d), L.stream_ptr(dev)), "cg_attn_stats")
     del keep
     return res
+
+
+# ---------------------------------------------------------------------------- structural regression probes
+SHAPE_TARGETS = 14  # CG_SHAPE_TARGETS
+
+
+def _rows_view(t, what):
+    """(tensor kept alive, rows, width, row stride) of a (rows, w) or (B, T, w) tensor whose rows are
+    evenly spaced with unit column stride (a column slice of a wider buffer included)."""
+    if t.dim() == 3:
+        B, T, w = t.shape
+        if B > 1 and T > 0 and t.stride(0) != T * t.stride(1):
+            t = t.contiguous()
+        rows, ld = B * T, t.stride(1)
+    elif t.dim() == 2:
+        rows, w = t.shape
+        ld = t.stride(0)
+    else:
+        raise ValueError(f"{what}: a (rows, w) or (B, T, w) tensor")
+    if w > 1 and t.stride(-1) != 1:
+        raise ValueError(f"{what}: unit column stride")
+    return t, rows, w, max(int(ld), w)
+
+
+def shape_targets(idx, codon_of, out=None):
+    """(y fp32 (B*T, 14), valid int32 (B*T)): the per-codon DNAshape targets of idx int64 (B, T)
+    (cg_shape_targets).  codon_of: one int per id, 6 bits = three 2-bit nucleotides (A, C, G, T =
+    0..3, first in the high bits), negative = not a codon.  Rows of non-codon positions are left as
+    they are (zeros in a fresh y).  out: a (B*T, >= 14) fp32 buffer to write into."""
+    L.require_device(idx, "shape_targets")
+    if idx.dim() != 2:
+        raise ValueError("shape_targets: idx is (B, T)")
+    idx = idx.to(torch.int64).contiguous()
+    B, T = idx.shape
+    tab = [int(v) for v in codon_of]
+    if len(tab) > 256:
+        raise ValueError("shape_targets: at most 256 ids")
+    y = torch.zeros(B * T, SHAPE_TARGETS, dtype=torch.float32, device=idx.device) if out is None else out
+    if y.dtype != torch.float32 or y.dim() != 2 or y.shape[0] != B * T or (y.numel() and y.stride(1) != 1):
+        raise ValueError("shape_targets: out must be fp32 (B*T, >= 14) with unit column stride")
+    ldy = max(int(y.stride(0)), y.shape[1]) if y.shape[1] else 0
+    valid = torch.empty(B * T, dtype=torch.int32, device=idx.device)
+    L.check(L.lib.cg_shape_targets(idx.data_ptr(), B, T, (C.c_int32 * max(len(tab), 1))(*tab), len(tab),
+                                   y.data_ptr(), ldy, valid.data_ptr(), L.stream_ptr(idx.device)),
+            "cg_shape_targets")
+    return y, valid
+
+
+def gram_workspace(rows, d, m, G, device):
+    """A cg_gram_accum workspace for these sizes (a uint8 tensor)."""
+    need = int(L.lib.cg_gram_workspace(int(rows), int(d), int(m), int(G)))
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+
+
+def gram_accum(h, y, grp, G, gram=None, *, m=None, accumulate=False, workspace=None):
+    """gram fp64 (G, P, P), P = d + m + 1: per group g the sum over the rows r with grp[r] == g of
+    z z^T, z = (h[r], y[r][:m], 1), accumulated in fp64 on the f64 MFMA (cg_gram_accum).  h: (rows, d)
+    or (B, T, d), fp32 or bf16, read in place; y: fp32 (rows, >= m) or None (m = 0); grp int32
+    (rows), rows with a value outside [0, G) are skipped and never read.  gram: the matrix to
+    overwrite (accumulate=False) or add to (accumulate=True); a (G, P, >= P) view of a wider
+    buffer is allowed.  workspace: a uint8 buffer to reuse (gram_workspace)."""
+    L.require_device(h, "gram_accum")
+    L.require_device(grp, "gram_accum")
+    h, rows, d, ldh = _rows_view(h, "gram_accum: h")
+    dev = h.device
+    if y is None:
+        if m not in (None, 0):
+            raise ValueError("gram_accum: m columns asked of no y")
+        m, ldy, yk = 0, 0, None
+    else:
+        L.require_device(y, "gram_accum")
+        if y.dtype != torch.float32:
+            raise ValueError("gram_accum: y must be fp32")
+        yk, yrows, wy, ldy = _rows_view(y, "gram_accum: y")
+        m = wy if m is None else int(m)
+        if yrows != rows or m > wy or m < 0:
+            raise ValueError("gram_accum: y must have h's rows and at least m columns")
+    if grp.dtype != torch.int32 or grp.numel() != rows or not grp.is_contiguous():
+        raise ValueError("gram_accum: grp must be a contiguous int32 (rows)")
+    G = int(G)
+    if G < 1:
+        raise ValueError("gram_accum: at least one group")
+    P = d + m + 1
+    if gram is None:
+        if accumulate:
+            raise ValueError("gram_accum: accumulate needs a gram to add to")
+        gram = torch.empty(G, P, P, dtype=torch.float64, device=dev)
+    L.require_device(gram, "gram_accum")
+    if (gram.dtype != torch.float64 or gram.dim() != 3 or tuple(gram.shape) != (G, P, P) or gram.stride(2) != 1
+            or (G > 1 and gram.stride(0) != P * gram.stride(1))):
+        raise ValueError("gram_accum: gram must be fp64 (G, P, P) with evenly spaced rows")
+    need = int(L.lib.cg_gram_workspace(rows, d, m, G))
+    ws = workspace
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = gram_workspace(rows, d, m, G, dev)
+    L.check(L.lib.cg_gram_accum(_dt(h), h.data_ptr(), ldh, d, _p(yk), ldy, m, grp.data_ptr(), rows, G,
+                                1 if accumulate else 0, gram.data_ptr(), max(int(gram.stride(1)), P), ws.data_ptr(),
+                                ws.numel() * ws.element_size(), L.stream_ptr(dev)), "cg_gram_accum")
+    return gram

@@ -1119,6 +1119,58 @@ int cg_attn_stats(const cg_attn_stats_desc* d, void* stream);
  * window and idx come from the model (as cg_model_attn_probs takes them), every other field from d */
 int cg_model_attn_stats(const cg_model* m, int layer, const cg_attn_stats_desc* d, void* stream);
 
+/* Structural regression probes (ABI 0.6 addition): per-codon DNAshape targets from token ids and the
+ * grouped augmented Gram matrix of hidden states and targets, from which every ridge fit, fold metric
+ * and principal component of the probes follows on a (d + m + 1)^2 matrix.  Replaces the per-sequence
+ * host copies and the N x d regression matrix of the reference's scripts/probe_structural_regression.py
+ * (:88-128) and scripts/probe_structural_awareness.py.
+ *
+ * cg_shape_targets (probe_structural_awareness.py:8-167 get_theoretical_shape, and the per-codon
+ * pooling of probe_structural_regression.py:116-121): idx device int64 [B][T]; codon_of host int32 [V],
+ * V <= 256: 6 bits = three 2-bit nucleotides, the first in the high bits, A, C, G, T = 0..3; negative =
+ * not a codon; an id outside 0..V-1 is not a codon.  A run is a maximal stretch of codon tokens inside
+ * one row of idx, its DNA the concatenation of its codons.  Nucleotide i of a run of L nucleotides
+ * sees the window dna[max(0, i-2) : min(L, i+3)] (never across a run or row boundary); each of the
+ * CG_SHAPE_TARGETS values of a nucleotide is the first rule whose word occurs in the window:
+ *    0 MGW      AAAA 3.5;  GGGG | CCCC 5.8;  else 4.5       7 Shift    AA | TT 0.0;  GC 0.2;  else -0.1
+ *    1 Roll     GC | CG 5.0;  AA | TT 0.0;  else 2.5        8 Tilt     AA 0.0;  CG 0.5;  else -0.2
+ *    2 EP       AAAA -10;  GGCC -2;  else -5                9 Buckle   GC -12;  AT 0;  else -6
+ *    3 ProT     GC -11;  AT -18;  else -14                 10 Opening  AT 2.0;  GC 0.5;  else 1.0
+ *    4 HelT     CG 36;  TA 32;  else 34                    11 Shear    GC 0.0;  else 0.1
+ *    5 Slide    AAAA -0.8;  GC | CG 0.2;  else -0.3        12 Stagger  AA 0.1;  else -0.1
+ *    6 Rise     CG 3.2;  AA 3.4;  else 3.3                 13 Stretch  CG -0.1;  else 0.0
+ * y[b*T + t][k] (fp32 [B*T][ldy]) = ((v0 + v1) + v2) / 3 of the codon's three nucleotides in fp64,
+ * rounded once to fp32; valid[b*T + t] = 1.  A position that holds no codon gets valid = 0 and its y
+ * row is not written; columns [CG_SHAPE_TARGETS, ldy) are never written.
+ * B == 0 or T == 0: CG_OK, nothing touched.  CG_EINVAL: NULL idx / y / valid / codon_of (V > 0), a
+ * negative size, V > 256, a table entry above 63, ldy < CG_SHAPE_TARGETS. */
+#define CG_SHAPE_TARGETS 14
+int cg_shape_targets(const int64_t* idx, int B, int T, const int32_t* codon_of, int V, float* y, long long ldy,
+                     int32_t* valid, void* stream);
+/* cg_gram_accum: h is a hidden-state buffer as cg_model_hidden returns it ([rows][ldh], CG_F32 or
+ * CG_BF16, d used columns), y fp32 [rows][ldy] with m >= 0 used columns, grp device int32 [rows].
+ * Row r belongs to group grp[r] when 0 <= grp[r] < G; any other row is skipped and its h and y are
+ * never read (they may hold NaN).  With z_r = (h[r][0..d), y[r][0..m), 1) and P = d + m + 1,
+ *   gram[g][i][j] (fp64 [G][P][ldg]) (+)= sum over the rows r of group g of z_r[i] * z_r[j],
+ * so gram[g][P-1][P-1] counts the group's rows (X^T X, X^T y, y^T y and the column sums of
+ * probe_structural_regression.py:165-178 for every fold at once).  accumulate = 1 adds the call's sums
+ * to what gram holds, accumulate = 0 overwrites all G * P * P entries (zeros for an empty group).
+ * The inputs are widened exactly to fp64; products and sums are fp64 on v_mfma_f64_16x16x4_f64.
+ * Order: the rows of a group, ascending, are cut into S slices of equal length (S fixed by rows, P
+ * and G); a slice's rows are added in order, four to an MFMA step, into one partial per 64 x 64
+ * block of the upper triangle, and the partials in slice order.  Element (i, j) and (j, i) are the same
+ * sum, so the call's sums are symmetric bitwise, and the same calls give the same bits.  No
+ * floating-point atomics.  The pad columns of h, y and gram are neither read nor written.
+ * rows == 0: CG_OK; with accumulate = 1 nothing is touched, otherwise gram is zeroed.
+ * CG_EINVAL: NULL gram, NULL h (d > 0) / y (m > 0) / grp / workspace with rows > 0, a negative size,
+ * rows above 2^30, G < 1, ldh < d, ldy < m, ldg < P, accumulate outside 0 / 1, ws_bytes below
+ * cg_gram_workspace(rows, d, m, G) or a workspace not 256-byte aligned.  CG_EUNSUPPORTED: another
+ * dtype, P > 8192 or G > 4096 (cg_gram_workspace returns 0 for those and for invalid sizes). */
+size_t cg_gram_workspace(long long rows, int d, int m, int G);
+int cg_gram_accum(int dtype, const void* h, long long ldh, int d, const float* y, long long ldy, int m,
+                  const int32_t* grp, long long rows, int G, int accumulate, double* gram, long long ldg,
+                  void* workspace, size_t ws_bytes, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -1185,7 +1237,8 @@ size_t cg_struct_bytes(const char* name);
  * diagnostic -- cg_ngram_count, cg_ngram_totals, cg_ngram_nll with cg_ngram_nll_desc and
  * cg_ngram_nll_workspace, cg_diag_rows with cg_diag_desc and cg_diag_workspace.  ABI 0.6, additions:
  * attention head analysis -- cg_attn_stats with cg_attn_stats_desc, cg_attn_stats_workspace and
- * cg_model_attn_stats. */
+ * cg_model_attn_stats.  ABI 0.6, additions: structural regression probes -- cg_shape_targets,
+ * cg_gram_accum and cg_gram_workspace. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

@@ -8,37 +8,10 @@ namespace {
 constexpr int AT_WAVES = 4;    // rows per workgroup pass
 constexpr int AT_BLK = 4096;   // grid cap; rows beyond 4 * AT_BLK are grid-strided
 
-int attr_blocks(long long rows) {
-  const long long b = (rows + AT_WAVES - 1) / AT_WAVES;
-  return (int)(b > AT_BLK ? AT_BLK : (b < 1 ? 1 : b));
-}
+int attr_blocks(long long rows) { return cg_grid_cap((rows + AT_WAVES - 1) / AT_WAVES, AT_BLK); }
 
-// fp64 wave sum: a fixed xor butterfly, every lane ends with the total (one sum per row, so the
-// LDS-routed shuffles of a 64-bit value do not matter here)
-__device__ __forceinline__ double wave_sum_d(double v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
-// the dlogits element layouts of cg_cross_entropy (ops.hip st_grad): fp32, or split bf16 with
-// hi = bf16(g) at column c and lo = bf16(g - hi) at column half + c
-template <typename TD, bool SPLIT>
-__device__ __forceinline__ void st_seed(TD* dr, long long c, long long half, float g) {
-  if constexpr (SPLIT) {
-    const bf16_t hi = f2bf(g);
-    dr[c] = hi;
-    dr[half + c] = f2bf(g - bf2f(hi));
-  } else {
-    dr[c] = g;
-  }
-}
-
-// d[r][c] = w (delta_{c,y} - softmax(z_r)_c) (LOGPROB) or w delta_{c,y} (LOGIT); a row with y
+// d[r][c] = w (delta_{c,y} - softmax(z_r)_c) (LOGPROB) or w delta_{c,y} (LOGIT), in the dlogits
+// element layouts of cg_cross_entropy (common.h st_grad: fp32 or split bf16); a row with y
 // outside [0, V) or w == 0 is all zero; columns [V, half) are zero in every row.  The softmax is
 // evaluated in fp64 from the fp32 logits and rounded once: rest = sum_{c != y} exp(z_c - max) is a
 // sum of non-negative terms, so d_y = w rest / (rest + e_y) keeps its relative accuracy however
@@ -55,11 +28,11 @@ __global__ __launch_bounds__(64 * AT_WAVES) void attr_seed_kernel(const float* _
     const long long t = y[row];
     const float wr = w ? w[row] : 1.0f;
     if (t < 0 || t >= V || wr == 0.0f) {
-      for (long long c = lane; c < half; c += 64) st_seed<TD, SPLIT>(dr, c, half, 0.f);
+      for (long long c = lane; c < half; c += 64) st_grad<TD, SPLIT>(dr, c, half, 0.f);
       continue;
     }
     if (mode == CG_ATTR_LOGIT) {
-      for (long long c = lane; c < half; c += 64) st_seed<TD, SPLIT>(dr, c, half, c == t ? wr : 0.f);
+      for (long long c = lane; c < half; c += 64) st_grad<TD, SPLIT>(dr, c, half, c == t ? wr : 0.f);
       continue;
     }
     const float* __restrict__ z = logits + row * ldl;
@@ -69,12 +42,12 @@ __global__ __launch_bounds__(64 * AT_WAVES) void attr_seed_kernel(const float* _
     double rest = 0.0;
     for (int c = lane; c < V; c += 64)
       if (c != t) rest += exp((double)z[c] - m);
-    rest = wave_sum_d(rest);
+    rest = wave_sum(rest);
     const double scale = (double)wr / (rest + exp((double)z[t] - m));
     for (long long c = lane; c < half; c += 64) {
       float g = 0.f;
       if (c < V) g = (float)(c == t ? scale * rest : -scale * exp((double)z[c] - m));
-      st_seed<TD, SPLIT>(dr, c, half, g);
+      st_grad<TD, SPLIT>(dr, c, half, g);
     }
   }
 }
@@ -85,8 +58,7 @@ __global__ __launch_bounds__(64 * AT_WAVES) void attr_seed_kernel(const float* _
 template <bool VEC>
 __device__ __forceinline__ void ld4(const float* __restrict__ p, int k0, int d, float* v) {
   if constexpr (VEC) {
-    const float4 q = *(const float4*)(p + k0);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    ld_vec<4>(p + k0, v);
   } else {
 #pragma unroll
     for (int u = 0; u < 4; ++u) v[u] = k0 + u < d ? p[k0 + u] : 0.f;
@@ -143,7 +115,6 @@ __global__ __launch_bounds__(64 * AT_WAVES) void attr_reduce_kernel(const float*
   }
 }
 
-inline bool row16(const void* p, long long ld) { return ((uintptr_t)p & 15) == 0 && (ld & 3) == 0; }
 }  // namespace
 
 extern "C" int cg_attr_seed(const float* logits, long long ldl, const int64_t* y, const float* w, int rows, int V,
@@ -175,7 +146,7 @@ extern "C" int cg_attr_reduce(const float* g, long long ldg, const int64_t* idx,
   if (gxt && (!tok_emb || ld_e < d || V <= 0)) return CG_EINVAL;
   if (gxi && (!x0 || ldx < d)) return CG_EINVAL;
   if (!gxt && !gxi && !gnorm) return CG_OK;
-  const bool vec = d % 4 == 0 && row16(g, ldg) && (!gxt || row16(tok_emb, ld_e)) && (!gxi || row16(x0, ldx));
+  const bool vec = d % 4 == 0 && cg_rows16(g, ldg, 4) && (!gxt || cg_rows16(tok_emb, ld_e, 4)) && (!gxi || cg_rows16(x0, ldx, 4));
   const dim3 grid(attr_blocks(rows)), block(64 * AT_WAVES);
   hipStream_t s = (hipStream_t)stream;
   if (vec)

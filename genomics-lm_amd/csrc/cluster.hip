@@ -6,15 +6,11 @@
 #include "common.h"
 
 namespace {
-struct IdMask {
-  uint32_t w[8];  // ids 0..255
-};
-
 inline int win_count(int T, int window, int stride) { return T >= window ? (T - window) / stride + 1 : 0; }
 
 // one thread per window: any token of it in the mask clears the flag
 __global__ __launch_bounds__(256) void window_keep_kernel(const int64_t* __restrict__ idx, long long nw_total,
-                                                          int nwin, int T, int window, int stride, IdMask em,
+                                                          int nwin, int T, int window, int stride, cg_id_mask em,
                                                           int32_t* __restrict__ keep) {
   const long long w = (long long)blockIdx.x * 256 + threadIdx.x;
   if (w >= nw_total) return;
@@ -22,10 +18,8 @@ __global__ __launch_bounds__(256) void window_keep_kernel(const int64_t* __restr
   const int j = (int)(w - b * nwin);
   const int64_t* row = idx + b * T + (long long)j * stride;
   int ok = 1;
-  for (int t = 0; t < window; ++t) {
-    const int64_t v = row[t];
-    if (v >= 0 && v < 256 && ((em.w[v >> 5] >> (v & 31)) & 1u)) ok = 0;
-  }
+  for (int t = 0; t < window; ++t)
+    if (cg_mask_has(em, row[t])) ok = 0;
   keep[w] = ok;
 }
 
@@ -70,16 +64,6 @@ constexpr int KM_ROWS = 128;  // points per assign workgroup
 constexpr int KM_DK = 32;     // columns per LDS stage
 constexpr int KM_LD = 36;     // row stride of a staged tile in floats (16-byte aligned rows)
 constexpr int KM_COLS = 64;   // columns per statistics workgroup
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void kmeans_cnorm_kernel(const float* __restrict__ cen, long long ldc, int k, int d,
                                                            int kpad, float* __restrict__ cn) {
@@ -224,7 +208,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restr
   }
   __syncthreads();
   if (wave == 0) {
-    const double v = wave_sum_d((double)dd[lane] + (double)dd[lane + 64]);
+    const double v = wave_sum((double)dd[lane] + (double)dd[lane + 64]);
     if (lane == 0) ipart[blockIdx.x] = v;
   }
 }
@@ -334,7 +318,6 @@ inline int km_sub(int k) {
   while (sub > 1 && sub * k * (KM_COLS * 4 + 4) > 65536) sub >>= 1;
   return sub;
 }
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 struct KmLayout {
   size_t cn, ipart, cpart, part, total;
   long long nblk, nchunk;
@@ -344,10 +327,10 @@ inline KmLayout km_layout(long long n, int d, int k) {
   L.nblk = (n + KM_ROWS - 1) / KM_ROWS;
   L.nchunk = (n + CG_KMEANS_CHUNK - 1) / CG_KMEANS_CHUNK;
   L.cn = 0;
-  L.ipart = up16(256 * sizeof(float));
-  L.cpart = L.ipart + up16((size_t)L.nblk * sizeof(double));
-  L.part = L.cpart + up16((size_t)L.nchunk * k * sizeof(int32_t));
-  L.total = L.part + up16((size_t)L.nchunk * k * d * sizeof(float));
+  L.ipart = cg_rup(256 * sizeof(float), 16);
+  L.cpart = L.ipart + cg_rup((size_t)L.nblk * sizeof(double), 16);
+  L.part = L.cpart + cg_rup((size_t)L.nchunk * k * sizeof(int32_t), 16);
+  L.total = L.part + cg_rup((size_t)L.nchunk * k * d * sizeof(float), 16);
   return L;
 }
 }  // namespace
@@ -357,9 +340,8 @@ extern "C" int cg_window_keep(const int64_t* idx, int B, int T, int window, int 
   if (B < 0 || T < 0 || window < 1 || stride < 1) return CG_EINVAL;
   const int nwin = win_count(T, window, stride);
   if (B == 0 || nwin == 0) return CG_OK;
-  if (!idx || !exclude_mask || !keep) return CG_EINVAL;
-  IdMask em;
-  for (int i = 0; i < 8; ++i) em.w[i] = exclude_mask[i];
+  cg_id_mask em;
+  if (!idx || !keep || !cg_mask_fill(em, exclude_mask)) return CG_EINVAL;
   const long long total = (long long)B * nwin;
   hipLaunchKernelGGL(window_keep_kernel, dim3(cg_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, idx, total,
                      nwin, T, window, stride, em, keep);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <mutex>
+#include <type_traits>
 #include "../../include/codonlm_hip.h"
 #include "probe.h"
 
@@ -34,29 +35,168 @@ template <typename T> __device__ __forceinline__ void st_act(T* p, float v);
 template <> __device__ __forceinline__ void st_act<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void st_act<bf16_t>(bf16_t* p, float v) { *p = f2bf(v); }
 
+// N = 2, 4 or 8 consecutive elements of a row as floats, p aligned to the whole run (fp32 N = 8:
+// to 16 bytes).  One access per run: float2 / float4 / two float4, or for bf16 uint32 / uint2 /
+// uint4, widened exactly.
+template <int N>
+__device__ __forceinline__ void ld_vec(const float* p, float* v) {
+  if constexpr (N == 8) {
+    const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else if constexpr (N == 4) {
+    const float4 a = *(const float4*)p;
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  } else {
+    const float2 a = *(const float2*)p;
+    v[0] = a.x; v[1] = a.y;
+  }
+}
+template <int N>
+__device__ __forceinline__ void ld_vec(const bf16_t* p, float* v) {
+  uint32_t u[N / 2];
+  if constexpr (N == 8) {
+    const uint4 t = *(const uint4*)p;
+    u[0] = t.x; u[1] = t.y; u[2] = t.z; u[3] = t.w;
+  } else if constexpr (N == 4) {
+    const uint2 t = *(const uint2*)p;
+    u[0] = t.x; u[1] = t.y;
+  } else {
+    u[0] = *(const uint32_t*)p;
+  }
+#pragma unroll
+  for (int j = 0; j < N / 2; ++j) {
+    v[2 * j] = __uint_as_float(u[j] << 16);
+    v[2 * j + 1] = __uint_as_float(u[j] & 0xFFFF0000u);
+  }
+}
+template <int N>
+__device__ __forceinline__ void st_vec(float* p, const float* v) {
+  if constexpr (N == 8) {
+    ((float4*)p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+    ((float4*)p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+  } else if constexpr (N == 4) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    *(float2*)p = make_float2(v[0], v[1]);
+  }
+}
+template <int N>
+__device__ __forceinline__ void st_vec(bf16_t* p, const float* v) {
+  uint32_t u[N / 2];
+#pragma unroll
+  for (int j = 0; j < N / 2; ++j) u[j] = (uint32_t)f2bf(v[2 * j]) | ((uint32_t)f2bf(v[2 * j + 1]) << 16);
+  if constexpr (N == 8) *(uint4*)p = make_uint4(u[0], u[1], u[2], u[3]);
+  else if constexpr (N == 4) *(uint2*)p = make_uint2(u[0], u[1]);
+  else *(uint32_t*)p = u[0];
+}
+// every row of a matrix of es-byte elements starts 16-byte aligned
+static inline bool cg_rows16(const void* p, long long ld, int es) {
+  return ((uintptr_t)p % 16) == 0 && (ld * es) % 16 == 0;
+}
+
+// SPLIT (dtype CG_BF16X2): g is stored as bf16 hi = bf16(g) at column c and bf16 lo =
+// bf16(g - hi) at column ldd/2 + c, so a bf16 MFMA product over [hi | lo] x [W; W] sees g to
+// ~16 significant bits (the tied-head dX product feeds ln_f's bias gradient, a column sum
+// over all tokens that cancels to a small value: 8-bit dlogits leave ~10% error in it).
+template <typename TD, bool SPLIT = false, typename I>
+__device__ __forceinline__ void st_grad(TD* dr, I c, long long half, float g) {
+  if constexpr (SPLIT) {
+    const bf16_t hi = f2bf(g);
+    dr[c] = hi;
+    dr[half + c] = f2bf(g - bf2f(hi));
+  } else {
+    st_act<TD>(dr + c, g);
+  }
+}
+
+// a set of token ids 0..255 as a bit mask, passed to kernels by value
+struct cg_id_mask {
+  uint32_t w[8];
+};
+// (no short-circuit: the callers test one token per loop trip, and a branch there would make the
+// trip wait for its outstanding loads)
+__device__ __forceinline__ bool cg_mask_has(const cg_id_mask& m, long long v) {
+  return ((unsigned long long)v < 256) & ((m.w[(v >> 5) & 7] >> (v & 31)) & 1u);
+}
+static inline bool cg_mask_fill(cg_id_mask& m, const uint32_t* words) {
+  if (!words) return false;
+  for (int i = 0; i < 8; ++i) m.w[i] = words[i];
+  return true;
+}
+
 // ---------------------------------------------------------------------------
 // wave / block reductions (64 lanes)
 // ---------------------------------------------------------------------------
 // All in VALU (no LDS round trip per step, as __shfl_xor's ds_bpermute would take): DPP within
 // each 16-lane row (quad xor 1, quad xor 2, row_half_mirror, row_mirror), then
 // v_permlane16_swap and v_permlane32_swap, whose two results called with (v, v) are the two
-// partners' values in every lane.  Every lane ends with the total, in a fixed order.
-template <typename F>
-__device__ __forceinline__ float wave_reduce(float v, F op) {
-  v = op(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false)));
-  v = op(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false)));
-  v = op(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, false)));
-  v = op(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, false)));
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = op(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return op(__uint_as_float(b[0]), __uint_as_float(b[1]));
+// partners' values in every lane.  Every lane ends with the total, in a fixed order: at each of
+// the six levels a lane combines its group's total with the partner group's, which is the tree of
+// an xor butterfly with the operands of some lanes swapped (op must be commutative).
+// T: any trivially copyable 4- or 8-byte value; each step moves its 32-bit words.
+template <typename T> struct cg_words { uint32_t w[sizeof(T) / 4]; };
+template <int CTRL, typename T>
+__device__ __forceinline__ T wave_dpp(T v) {
+  cg_words<T> u = __builtin_bit_cast(cg_words<T>, v);
+#pragma unroll
+  for (int j = 0; j < (int)(sizeof(T) / 4); ++j)
+    u.w[j] = (uint32_t)__builtin_amdgcn_mov_dpp((int)u.w[j], CTRL, 0xF, 0xF, false);
+  return __builtin_bit_cast(T, u);
 }
-__device__ __forceinline__ float wave_sum(float v) {
-  return wave_reduce(v, [](float a, float b) { return a + b; });
+// a, b = the lane's own value and that of its partner 16 (WIDE: 32) lanes away, in either order
+template <bool WIDE, typename T>
+__device__ __forceinline__ void wave_swap(T v, T& a, T& b) {
+  const cg_words<T> u = __builtin_bit_cast(cg_words<T>, v);
+  cg_words<T> x, y;
+#pragma unroll
+  for (int j = 0; j < (int)(sizeof(T) / 4); ++j) {
+    if constexpr (WIDE) {
+      const auto r = __builtin_amdgcn_permlane32_swap(u.w[j], u.w[j], false, false);
+      x.w[j] = r[0]; y.w[j] = r[1];
+    } else {
+      const auto r = __builtin_amdgcn_permlane16_swap(u.w[j], u.w[j], false, false);
+      x.w[j] = r[0]; y.w[j] = r[1];
+    }
+  }
+  a = __builtin_bit_cast(T, x);
+  b = __builtin_bit_cast(T, y);
+}
+template <typename T, typename F>
+__device__ __forceinline__ T wave_reduce(T v, F op) {
+  static_assert((sizeof(T) == 4 || sizeof(T) == 8) && std::is_trivially_copyable<T>::value, "4- or 8-byte values");
+  v = op(v, wave_dpp<0xB1>(v));
+  v = op(v, wave_dpp<0x4E>(v));
+  v = op(v, wave_dpp<0x141>(v));
+  v = op(v, wave_dpp<0x140>(v));
+  T a, b;
+  wave_swap<false>(v, a, b);
+  v = op(a, b);
+  wave_swap<true>(v, a, b);
+  return op(a, b);
+}
+// float, double, int or long long
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+  return wave_reduce(v, [](T a, T b) { return a + b; });
 }
 __device__ __forceinline__ float wave_max(float v) {
   return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); });
+}
+__device__ __forceinline__ int wave_min(int v) {
+  return wave_reduce(v, [](int a, int b) { return a < b ? a : b; });
+}
+
+// sum over the 1024 threads of a workgroup of one value each, through red[1024] in LDS: a halving
+// tree in a fixed order.  The total is left in red[0] for any thread to read (the last step ends
+// with a barrier); a barrier before red is written again.
+template <typename T>
+__device__ __forceinline__ void block_sum_1024(T s, T* red) {
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -221,3 +361,7 @@ static inline void cg_func_lds(const void* fn, int bytes) {
   } while (0)
 
 static inline int cg_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// a launch grid of n workgroups clamped to [1, cap]; the kernel grid-strides over the rest
+static inline int cg_grid_cap(long long n, int cap) { return n > cap ? cap : (n < 1 ? 1 : (int)n); }
+// v rounded up to a multiple of a (workspace layouts)
+static inline size_t cg_rup(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -17,30 +17,14 @@ constexpr int DG_CAL = 2 * CG_DIAG_SLICES;             // first calibration accu
 constexpr int DG_BRIER = DG_CAL + 3 * CG_DIAG_MAX_BINS;  // the two Brier accumulators
 constexpr int DG_NACC = DG_BRIER + 2;
 
-struct IdMask { uint32_t w[8]; };
-
-// butterfly over the 64 lanes: every lane ends with the total, in a fixed order
-template <typename T, typename F>
-__device__ __forceinline__ T wave_all(T v, F op) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = op(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wsum_d(double v) {
-  return wave_all(v, [](double a, double b) { return a + b; });
-}
-__device__ __forceinline__ int wsum_i(int v) {
-  return wave_all(v, [](int a, int b) { return a + b; });
-}
 __device__ __forceinline__ bool in_vocab(long long t, int V) { return t >= 0 && t < V; }
-__device__ __forceinline__ bool is_reset(const IdMask& m, int tok) { return (m.w[tok >> 5] >> (tok & 31)) & 1u; }
 
 // ------------------------------------------------------------------ counting
 // grid-stride over the flat positions; the bigram table of the workgroup lives in LDS as 32-bit
 // counts (a workgroup sees fewer than 2^32 positions: the entry point bounds n), the unigram counts
 // are its column sums
 __global__ __launch_bounds__(256) void ngram_count_kernel(const int64_t* __restrict__ x, const int64_t* __restrict__ y,
-                                                          long long n, int T, int V, int pad, IdMask reset,
+                                                          long long n, int T, int V, int pad, cg_id_mask reset,
                                                           unsigned long long* __restrict__ uni,
                                                           unsigned long long* __restrict__ bi,
                                                           unsigned long long* __restrict__ tri,
@@ -60,7 +44,7 @@ __global__ __launch_bounds__(256) void ngram_count_kernel(const int64_t* __restr
       const long long p = x[i];
       if (in_vocab(yy, V) && in_vocab(p, V)) {
         long long p2 = pad;
-        if (t != 0 && !is_reset(reset, (int)p)) p2 = x[i - 1];
+        if (t != 0 && !cg_mask_has(reset, p)) p2 = x[i - 1];
         if (in_vocab(p2, V)) {
           atomicAdd(&cnt[(int)p * V + (int)yy], 1u);
           atomicAdd(&tri[((long long)p2 * V + p) * V + yy], 1ull);
@@ -106,14 +90,14 @@ __global__ __launch_bounds__(256) void ngram_totals_kernel(const long long* __re
   long long s = 0;
   for (int c = lane; c < V; c += 64)
     if (c >= 1) s += src[c];
-  s = wave_all(s, [](long long a, long long b) { return a + b; });
+  s = wave_sum(s);
   if (lane == 0) *dst = s;
 }
 
 struct NllArgs {
   const int64_t* x; const int64_t* y;
   int B, T, V, pad;
-  IdMask reset;
+  cg_id_mask reset;
   double alpha;
   const long long* uni; const long long* bi; const long long* tri;
   const long long* uni_total; const long long* bi_total; const long long* tri_total;
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(64 * NG_WAVES) void ngram_nll_kernel(NllArgs A) {
         const long long p = A.x[base + t];
         if (in_vocab(yy, V) && in_vocab(p, V)) {
           long long p2 = A.pad;
-          if (t != 0 && !is_reset(A.reset, (int)p)) p2 = A.x[base + t - 1];
+          if (t != 0 && !cg_mask_has(A.reset, p)) p2 = A.x[base + t - 1];
           if (in_vocab(p2, V)) {
             const double cu = (double)A.uni[yy];
             const double cb = (double)A.bi[p * V + yy], tb = (double)A.bi_total[p];
@@ -159,8 +143,8 @@ __global__ __launch_bounds__(64 * NG_WAVES) void ngram_nll_kernel(NllArgs A) {
       }
       if (A.tok_tri) A.tok_tri[base + t] = out;
     }
-    s_uni = wsum_d(s_uni); s_bi = wsum_d(s_bi); s_tri = wsum_d(s_tri);
-    n = wsum_i(n);
+    s_uni = wave_sum(s_uni); s_bi = wave_sum(s_bi); s_tri = wave_sum(s_tri);
+    n = wave_sum(n);
     const double s_flat = (double)n * lg_uniform;
     if (lane == 0) {
       if (A.row_sums) {
@@ -276,15 +260,15 @@ __global__ __launch_bounds__(DG_CHUNK) void diag_rows_kernel(DiagArgs A) {
         float mloc = z0;
         int iloc = lane;
         if (z1 > mloc) { mloc = z1; iloc = lane + 64; }
-        const float mx = wave_all(mloc, [](float a, float b) { return fmaxf(a, b); });
-        const int amax = wave_all(mloc == mx ? iloc : INT_MAX, [](int a, int b) { return a < b ? a : b; });
+        const float mx = wave_max(mloc);
+        const int amax = wave_min(mloc == mx ? iloc : INT_MAX);
         // s1 = sum over c != argmax of exp(z - max) (that term is exactly 1), s2 of its square
         const double m = (double)mx;
         double s1 = 0.0, s2 = 0.0;
         if (lane < V && lane != amax) { const double e = exp((double)z0 - m); s1 += e; s2 += e * e; }
         if (lane + 64 < V && lane + 64 != amax) { const double e = exp((double)z1 - m); s1 += e; s2 += e * e; }
-        s1 = wsum_d(s1);
-        s2 = wsum_d(s2);
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
         const double lgs = log1p(s1);            // lse - max
         const double dzy = (double)zr[yj] - m;   // <= 0
         const double nll = lgs - dzy;
@@ -335,8 +319,8 @@ __global__ __launch_bounds__(DG_CHUNK) void diag_rows_kernel(DiagArgs A) {
       __syncthreads();
     }
     if (wave == 0 && (A.row_nll || A.row_count)) {
-      rs = wsum_d(rs);
-      rc = wsum_i(rc);
+      rs = wave_sum(rs);
+      rc = wave_sum(rc);
       if (lane == 0) {
         if (A.row_nll) A.row_nll[b] = rs;
         if (A.row_count) A.row_count[b] = rc;
@@ -364,14 +348,8 @@ __global__ __launch_bounds__(DG_NACC) void diag_final_kernel(const double* __res
   *dst += s;
 }
 
-int capped(long long n, int cap) { return n > cap ? cap : (n < 1 ? 1 : (int)n); }
-int nll_blocks(int B) { return capped(cg_cdiv(B, NG_WAVES), NG_BLK); }
-int diag_blocks(int B) { return capped(B, DG_BLK); }
-bool mask_from_host(const uint32_t* words, IdMask& m) {
-  if (!words) return false;
-  for (int i = 0; i < 8; ++i) m.w[i] = words[i];
-  return true;
-}
+int nll_blocks(int B) { return cg_grid_cap(cg_cdiv(B, NG_WAVES), NG_BLK); }
+int diag_blocks(int B) { return cg_grid_cap(B, DG_BLK); }
 }  // namespace
 
 extern "C" int cg_ngram_count(const int64_t* x, const int64_t* y, int B, int T, int V, int pad_id,
@@ -381,11 +359,11 @@ extern "C" int cg_ngram_count(const int64_t* x, const int64_t* y, int B, int T, 
   if (V > NG_V) return CG_EUNSUPPORTED;
   if (pad_id < 0 || pad_id >= V) return CG_EINVAL;
   if (B == 0 || T == 0) return CG_OK;
-  IdMask m;
-  if (!x || !y || !uni || !bi || !tri || !mask_from_host(reset_mask, m)) return CG_EINVAL;
+  cg_id_mask m;
+  if (!x || !y || !uni || !bi || !tri || !cg_mask_fill(m, reset_mask)) return CG_EINVAL;
   const long long n = (long long)B * T;
   if (n > (1ll << 40)) return CG_EUNSUPPORTED;
-  const int nblk = capped((n + 256 * 8 - 1) / (256 * 8), NG_BLK);
+  const int nblk = cg_grid_cap((n + 256 * 8 - 1) / (256 * 8), NG_BLK);
   const int lds = V * V * (int)sizeof(uint32_t);
   cg_func_lds((const void*)ngram_count_kernel, lds);
   hipLaunchKernelGGL(ngram_count_kernel, dim3(nblk), dim3(256), lds, (hipStream_t)stream, x, y, n, T, V, pad_id, m,
@@ -417,7 +395,7 @@ extern "C" int cg_ngram_nll(const cg_ngram_nll_desc* d, void* stream) {
   if (d->pad_id < 0 || d->pad_id >= d->V || !(d->alpha > 0.0) || !isfinite(d->alpha)) return CG_EINVAL;
   if (d->B == 0 || d->T == 0) return CG_OK;
   NllArgs A;
-  if (!d->x || !d->y || !mask_from_host(d->reset_mask, A.reset)) return CG_EINVAL;
+  if (!d->x || !d->y || !cg_mask_fill(A.reset, d->reset_mask)) return CG_EINVAL;
   if (!d->uni || !d->bi || !d->tri || !d->uni_total || !d->bi_total || !d->tri_total) return CG_EINVAL;
   if (d->acc && (!d->workspace || ((uintptr_t)d->workspace & 7) || ((uintptr_t)d->acc & 7) ||
                  d->ws_bytes < cg_ngram_nll_workspace(d->B)))

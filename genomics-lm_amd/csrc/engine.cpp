@@ -1200,6 +1200,73 @@ int embed_backward(const Ctx& C, cg_model* m, uint32_t seed, float p, int accumu
                     accumulate, A.embws, A.nb.embws, C.s));
   return CG_OK;
 }
+
+// ---- The dX chain of block l, stated once for cg_model_backward phase 1 and cg_model_input_grad.
+// GELU MLP: sl.gin = dL/d(mlp out) -> sl.dmlp (dGELU product) -> A.dsmall = dL/d(ln2 out), compute
+// dtype.  cpart: where the dGELU product's fused column-sum epilogue leaves fc1's bias-gradient
+// partials (64-row partials), or null for no such epilogue.
+int mlp_dx_gelu(const Ctx& C, int l, const DwSlot& sl, float* cpart) {
+  const Dims& D = C.D;
+  const auto& o = C.Lo.lay[l];
+  const auto& a = C.A.la[l];
+  const int d = D.d;
+  cg_gemm_desc g = lin_dx(C, sl.gin, d, o.w2, D.hid, d, D.hid, sl.dmlp, D.hid, a.w2T);
+  g.epilogue = CG_EPI_DGELU | CG_EPI_GELU_DERIV | (cpart ? CG_EPI_COLSUM : 0); g.aux = a.a; g.ld_aux = D.hid;
+  if (cpart) {
+    g.workspace = cpart;
+    g.ws_bytes = C.A.nb.cpart;
+  }
+  CK(cg_gemm(&g, C.s));
+  g = lin_dx(C, sl.dmlp, D.hid, o.w1, d, D.hid, d, C.A.dsmall, d, a.w1T);
+  return cg_gemm(&g, C.s);
+}
+// SwiGLU MLP: the dL/ds product with the SwiGLU backward in its epilogue (d(gate|up) straight to
+// sl.dmlp; fp32 parity mode: the plain product and cg_swiglu_bwd), then A.dsmall = dL/d(ln2 out)
+int mlp_dx_swiglu(const Ctx& C, int l, const DwSlot& sl) {
+  const Dims& D = C.D;
+  const Acts& A = C.A;
+  const auto& o = C.Lo.lay[l];
+  const auto& a = A.la[l];
+  const int d = D.d;
+  cg_gemm_desc g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, sl.dmlp, 2 * D.Hp, a.wdT);
+  g.epilogue = CG_EPI_DSWIGLU; g.aux = a.gu; g.ld_aux = 2 * D.Hp; g.n_valid = D.hid;
+  int rc = C.dt == CG_BF16 ? cg_gemm(&g, C.s) : CG_EUNSUPPORTED;
+  if (rc == CG_EUNSUPPORTED) {
+    g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, A.dsmall, D.Hp, a.wdT);
+    CK(cg_gemm(&g, C.s));
+    rc = cg_swiglu_bwd(C.dt, a.gu, 2 * D.Hp, D.Hp, A.dsmall, D.Hp, sl.dmlp, 2 * D.Hp, (int)C.M, D.hid, C.s);
+  }
+  CK(rc);
+  g = lin_dx(C, sl.dmlp, 2 * D.Hp, o.wgu, d, 2 * D.Hp, d, A.dsmall, d, a.wguT);
+  return cg_gemm(&g, C.s);
+}
+// Attention: A.dsmall = dL/d(attention out) -> sl.dqkv (un-rotated).  The MFMA backward leaves the
+// qkv bias gradient's column sums as per-tile partials in bpart (with RoPE it rotates dQ / dK back
+// before the stores and the partials); where it does not apply, the vector kernels and the table
+// inverse rotation run and bpart stays unwritten.  *fused_bias: the partials were produced.
+int attn_dx(const Ctx& C, int l, const DwSlot& sl, uint32_t seed, float p, const void* dmask, float* bpart,
+            long long ld_bpart, bool* fused_bias) {
+  const cg_model* m = C.m;
+  const Dims& D = C.D;
+  const Acts& A = C.A;
+  const auto& a = A.la[l];
+  const int d = D.d;
+  const int32_t* segp = m->cfg.sep_id >= 0 ? A.seg : nullptr;
+  const bool rope_in = D.rope && !m->cfg.opts.rope_tables;  // the inverse rotation inside the kernels
+  int rc = CG_EUNSUPPORTED;
+  if (!D.rope || rope_in)
+    rc = cg_attn_bwd_algo(m->cfg.opts.attn_bwd_algo, C.dt, a.qkv, D.Nqkv, segp, a.y, d, A.dsmall, d, a.lse, sl.dqkv,
+                          D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->window, seed, p, dmask, bpart, ld_bpart,
+                          rope_in ? m->rope_cos : nullptr, rope_in ? m->rope_sin : nullptr, A.delta, A.nb.delta, C.s);
+  *fused_bias = rc == CG_OK;
+  if (rc == CG_EUNSUPPORTED) {
+    rc = cg_attn_bwd(C.dt, a.qkv, D.Nqkv, segp, a.y, d, A.dsmall, d, a.lse, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd,
+                     m->window, seed, p, dmask, nullptr, 0, A.delta, A.nb.delta, C.s);
+    if (rc == CG_OK && D.rope)
+      rc = cg_rope_tab(C.dt, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->rope_cos, m->rope_sin, 1, C.s);
+  }
+  return rc;
+}
 }  // namespace
 
 extern "C" int cg_model_backward(cg_model* m, int phase, int layer, int accumulate, void* stream) {
@@ -1275,29 +1342,10 @@ extern "C" int cg_model_backward(cg_model* m, int phase, int layer, int accumula
       // cost this product 16-22 us per layer at C4), or -- when that launch splits the tokens --
       // by this product's fused column-sum epilogue (64-row partials)
       const bool in_dw = fc1_bias_in_dw(C, l);
-      cg_gemm_desc g = lin_dx(C, sl.gin, d, o.w2, D.hid, d, D.hid, sl.dmlp, D.hid, a.w2T);
-      g.epilogue = CG_EPI_DGELU | CG_EPI_GELU_DERIV | (in_dw ? 0 : CG_EPI_COLSUM); g.aux = a.a; g.ld_aux = D.hid;
-      if (!in_dw) {
-        g.workspace = sl.cpart;
-        g.ws_bytes = A.nb.cpart;
-      }
-      CK(cg_gemm(&g, C.s));
+      CK(mlp_dx_gelu(C, l, sl, in_dw ? nullptr : sl.cpart));
       if (!in_dw) CK(defer_reduce(m, sl.cpart, D.hid, (int)((M + 63) / 64), D.hid, G(C, o.b1), accumulate, C.s));
-      g = lin_dx(C, sl.dmlp, D.hid, o.w1, d, D.hid, d, A.dsmall, d, a.w1T);  // dL/d(ln2 out), compute dtype
-      CK(cg_gemm(&g, C.s));
     } else {
-      // dL/ds product with the SwiGLU backward in its epilogue (d(gate|up) straight to dmlp)
-      cg_gemm_desc g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, sl.dmlp, 2 * D.Hp, a.wdT);
-      g.epilogue = CG_EPI_DSWIGLU; g.aux = a.gu; g.ld_aux = 2 * D.Hp; g.n_valid = D.hid;
-      int rc = C.dt == CG_BF16 ? cg_gemm(&g, C.s) : CG_EUNSUPPORTED;
-      if (rc == CG_EUNSUPPORTED) {
-        g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, A.dsmall, D.Hp, a.wdT);
-        CK(cg_gemm(&g, C.s));
-        rc = cg_swiglu_bwd(C.dt, a.gu, 2 * D.Hp, D.Hp, A.dsmall, D.Hp, sl.dmlp, 2 * D.Hp, (int)M, D.hid, C.s);
-      }
-      CK(rc);
-      g = lin_dx(C, sl.dmlp, 2 * D.Hp, o.wgu, d, 2 * D.Hp, d, A.dsmall, d, a.wguT);
-      CK(cg_gemm(&g, C.s));
+      CK(mlp_dx_swiglu(C, l, sl));
     }
     // gattn = dL/d(proj out); its column sum is the proj bias gradient
     CK(ln_bwd_deferred(C, C.dt, A.dsmall, a.xmid, a.mean2, a.rstd2, o.ln2w, A.g, sl.gattn, 0, 0.f, sl.lnp2,
@@ -1305,29 +1353,10 @@ extern "C" int cg_model_backward(cg_model* m, int phase, int layer, int accumula
     // ---------------- attention branch
     cg_gemm_desc g = lin_dx(C, sl.gattn, d, o.wp, d, d, d, A.dsmall, d, a.pT);
     CK(cg_gemm(&g, C.s));
-    // the qkv bias gradient = column sums of the (un-rotated) dqkv: produced by the MFMA attention
-    // backward itself as per-tile partials (with RoPE it rotates dQ / dK back before the stores and
-    // the partials), else a colsum pass after the vector kernels and the table inverse rotation
-    const void* segp = m->cfg.sep_id >= 0 ? A.seg : nullptr;
-    const void* dmask_b = p > 0.f ? a.dmask : nullptr;
-    const bool rope_in = D.rope && !m->cfg.opts.rope_tables;  // the inverse rotation inside the kernels
-    const float* rc_cos = rope_in ? m->rope_cos : nullptr;
-    const float* rc_sin = rope_in ? m->rope_sin : nullptr;
-    int rc = CG_EUNSUPPORTED;
-    if (!D.rope || rope_in)
-      rc = cg_attn_bwd_algo(m->cfg.opts.attn_bwd_algo, C.dt, a.qkv, D.Nqkv, (const int32_t*)segp, a.y, d, A.dsmall,
-                            d, a.lse, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->window,
-                            site_seed(seed, l, SITE_ATTN), p, dmask_b, sl.bpart, D.Nqkv, rc_cos, rc_sin, A.delta,
-                            A.nb.delta, C.s);
-    const bool fused_bias = rc == CG_OK;
-    if (rc == CG_EUNSUPPORTED) {
-      rc = cg_attn_bwd(C.dt, a.qkv, D.Nqkv, (const int32_t*)segp, a.y, d, A.dsmall, d, a.lse, sl.dqkv, D.Nqkv, C.B,
-                       C.T, D.H, D.KV, D.hd, m->window, site_seed(seed, l, SITE_ATTN), p, dmask_b, nullptr, 0,
-                       A.delta, A.nb.delta, C.s);
-      if (rc == CG_OK && D.rope)
-        rc = cg_rope_tab(C.dt, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->rope_cos, m->rope_sin, 1, C.s);
-    }
-    CK(rc);
+    // the qkv bias gradient = column sums of the (un-rotated) dqkv: the attention backward's own
+    // per-tile partials where it produced them, else a colsum pass
+    bool fused_bias = false;
+    CK(attn_dx(C, l, sl, site_seed(seed, l, SITE_ATTN), p, p > 0.f ? a.dmask : nullptr, sl.bpart, D.Nqkv, &fused_bias));
     if (fused_bias)
       CK(defer_reduce(m, sl.bpart, D.Nqkv, C.B * ((C.T + 127) / 128), D.Nqkv, G(C, o.bqkv), accumulate, C.s));
     else
@@ -1410,49 +1439,18 @@ extern "C" int cg_model_input_grad(cg_model* m, const cg_attr_desc* a, void* str
   CK(cg_layernorm_bwd_partials(CG_F32, A.dtmp, d, A.x + (size_t)D.L * M * d, d, A.meanf, A.rstdf, P(C, C.Lo.lnfw),
                                nullptr, A.g, C.dt, D.L > 0 ? sl.gin : nullptr, 0, 0.f, A.lnpart, A.nb.lnp, 0, (int)M,
                                d, C.s));
-  const void* segp = m->cfg.sep_id >= 0 ? A.seg : nullptr;
-  const bool rope_in = D.rope && !m->cfg.opts.rope_tables;  // the inverse rotation inside the kernels
   for (int l = D.L - 1; l >= 0; --l) {
     const auto& o = C.Lo.lay[l];
     const auto& la = A.la[l];
     // MLP branch: sl.gin = dL/d(mlp out) -> A.dsmall = dL/d(ln2 out)
-    if (!D.swiglu) {
-      g = lin_dx(C, sl.gin, d, o.w2, D.hid, d, D.hid, sl.dmlp, D.hid, la.w2T);
-      g.epilogue = CG_EPI_DGELU | CG_EPI_GELU_DERIV; g.aux = la.a; g.ld_aux = D.hid;
-      CK(cg_gemm(&g, C.s));
-      g = lin_dx(C, sl.dmlp, D.hid, o.w1, d, D.hid, d, A.dsmall, d, la.w1T);
-      CK(cg_gemm(&g, C.s));
-    } else {
-      g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, sl.dmlp, 2 * D.Hp, la.wdT);
-      g.epilogue = CG_EPI_DSWIGLU; g.aux = la.gu; g.ld_aux = 2 * D.Hp; g.n_valid = D.hid;
-      int rc = C.dt == CG_BF16 ? cg_gemm(&g, C.s) : CG_EUNSUPPORTED;
-      if (rc == CG_EUNSUPPORTED) {
-        g = lin_dx(C, sl.gin, d, o.wd, D.Hp, d, D.Hp, A.dsmall, D.Hp, la.wdT);
-        CK(cg_gemm(&g, C.s));
-        rc = cg_swiglu_bwd(C.dt, la.gu, 2 * D.Hp, D.Hp, A.dsmall, D.Hp, sl.dmlp, 2 * D.Hp, (int)M, D.hid, C.s);
-      }
-      CK(rc);
-      g = lin_dx(C, sl.dmlp, 2 * D.Hp, o.wgu, d, 2 * D.Hp, d, A.dsmall, d, la.wguT);
-      CK(cg_gemm(&g, C.s));
-    }
+    CK(D.swiglu ? mlp_dx_swiglu(C, l, sl) : mlp_dx_gelu(C, l, sl, nullptr));
     CK(cg_layernorm_bwd_partials(C.dt, A.dsmall, d, la.xmid, d, la.mean2, la.rstd2, P(C, o.ln2w), A.g, A.g, C.dt,
                                  sl.gattn, 0, 0.f, sl.lnp2, A.nb.lnp, 0, (int)M, d, C.s));
     // attention branch: sl.gattn = dL/d(proj out) -> A.dsmall = dL/d(ln1 out)
     g = lin_dx(C, sl.gattn, d, o.wp, d, d, d, A.dsmall, d, la.pT);
     CK(cg_gemm(&g, C.s));
-    int rc = CG_EUNSUPPORTED;
-    if (!D.rope || rope_in)
-      rc = cg_attn_bwd_algo(m->cfg.opts.attn_bwd_algo, C.dt, la.qkv, D.Nqkv, (const int32_t*)segp, la.y, d, A.dsmall,
-                            d, la.lse, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->window, 0, 0.f, nullptr, nullptr,
-                            0, rope_in ? m->rope_cos : nullptr, rope_in ? m->rope_sin : nullptr, A.delta, A.nb.delta,
-                            C.s);
-    if (rc == CG_EUNSUPPORTED) {
-      rc = cg_attn_bwd(C.dt, la.qkv, D.Nqkv, (const int32_t*)segp, la.y, d, A.dsmall, d, la.lse, sl.dqkv, D.Nqkv, C.B,
-                       C.T, D.H, D.KV, D.hd, m->window, 0, 0.f, nullptr, nullptr, 0, A.delta, A.nb.delta, C.s);
-      if (rc == CG_OK && D.rope)
-        rc = cg_rope_tab(C.dt, sl.dqkv, D.Nqkv, C.B, C.T, D.H, D.KV, D.hd, m->rope_cos, m->rope_sin, 1, C.s);
-    }
-    CK(rc);
+    bool fused_bias;  // no bias gradient here: no partials asked for
+    CK(attn_dx(C, l, sl, 0, 0.f, nullptr, nullptr, 0, &fused_bias));
     g = lin_dx(C, sl.dqkv, D.Nqkv, o.wqkv, d, D.Nqkv, d, A.dsmall, d, la.qkvT);
     CK(cg_gemm(&g, C.s));
     CK(cg_layernorm_bwd_partials(C.dt, A.dsmall, d, A.x + (size_t)l * M * d, d, la.mean1, la.rstd1, P(C, o.ln1w), A.g,
@@ -1557,6 +1555,61 @@ int make_dec_ctx(const cg_model* m, int B, void* stream, Ctx& C) {
   C.s = (hipStream_t)stream;
   return CG_OK;
 }
+
+// ---- The parts of a decode step that do not depend on the rows' positions, stated once for
+// cg_model_decode and decode_ragged_body (embedding, segment state, RoPE, cache append and attention
+// do, and stay with their callers).
+inline float ln_eps_of(const cg_model* m) { return m->cfg.ln_eps > 0 ? m->cfg.ln_eps : 1e-5f; }
+// W.x -> LayerNorm 1 -> qkv product (+ bias) -> W.qkv
+int dec_ln1_qkv(const Ctx& C, const DecWS& W, int l) {
+  const Dims& D = C.D;
+  const auto& o = C.Lo.lay[l];
+  const int d = D.d;
+  CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, o.ln1w), P(C, o.ln1b), W.h, d, W.mean, W.rstd, C.B, d, ln_eps_of(C.m), C.s));
+  cg_gemm_desc g = lin_fwd(C, W.h, d, o.wqkv, d, D.Nqkv, d, W.qkv, D.Nqkv);
+  g.epilogue = CG_EPI_BIAS; g.bias = P(C, o.bqkv);
+  return cg_gemm(&g, C.s);
+}
+// W.y (attention out) -> proj (+ bias + W.x) -> W.xmid -> LayerNorm 2 -> MLP (+ W.xmid) -> W.x
+int dec_proj_mlp(const Ctx& C, const DecWS& W, int l) {
+  const Dims& D = C.D;
+  const auto& o = C.Lo.lay[l];
+  const int d = D.d, B = C.B;
+  cg_gemm_desc g = lin_fwd(C, W.y, d, o.wp, d, d, d, W.xmid, d);
+  g.c_dtype = CG_F32;
+  g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.bp); g.resid = W.x; g.ldr = d;
+  CK(cg_gemm(&g, C.s));
+  CK(cg_layernorm_fwd(C.dt, W.xmid, d, P(C, o.ln2w), P(C, o.ln2b), W.h, d, W.mean, W.rstd, B, d, ln_eps_of(C.m), C.s));
+  if (!D.swiglu) {
+    g = lin_fwd(C, W.h, d, o.w1, d, D.hid, d, W.g, D.hid);
+    g.epilogue = CG_EPI_BIAS | CG_EPI_GELU | CG_EPI_GELU_DERIV; g.bias = P(C, o.b1); g.aux_out = W.a; g.ld_aux = D.hid;
+    CK(cg_gemm(&g, C.s));
+    g = lin_fwd(C, W.g, D.hid, o.w2, D.hid, d, D.hid, W.x, d);
+    g.c_dtype = CG_F32;
+    g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.b2); g.resid = W.xmid; g.ldr = d;
+    return cg_gemm(&g, C.s);
+  }
+  g = lin_fwd(C, W.h, d, o.wgu, d, 2 * D.Hp, d, W.gu, 2 * D.Hp);
+  CK(cg_gemm(&g, C.s));
+  CK(cg_swiglu_fwd(C.dt, W.gu, 2 * D.Hp, D.Hp, W.s, D.Hp, B, D.hid, C.s));
+  g = lin_fwd(C, W.s, D.Hp, o.wd, D.Hp, d, D.Hp, W.x, d);
+  g.c_dtype = CG_F32;
+  g.epilogue = CG_EPI_RESID; g.resid = W.xmid; g.ldr = d;
+  return cg_gemm(&g, C.s);
+}
+// W.x -> ln_f -> W.xf
+int dec_ln_f(const Ctx& C, const DecWS& W) {
+  const int d = C.D.d;
+  return cg_layernorm_fwd(C.dt, W.x, d, P(C, C.Lo.lnfw), P(C, C.Lo.lnfb), W.xf, d, W.mean, W.rstd, C.B, d,
+                          ln_eps_of(C.m), C.s);
+}
+// W.xf -> head product -> out [B][V] fp32
+int dec_head(const Ctx& C, const DecWS& W, float* out) {
+  const long long hoff = C.m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head;
+  cg_gemm_desc g = lin_fwd(C, W.xf, C.D.d, hoff, C.D.d, C.D.V, C.D.d, out, C.D.V);
+  g.c_dtype = CG_F32;
+  return cg_gemm(&g, C.s);
+}
 }  // namespace
 
 extern "C" size_t cg_kv_cache_bytes(const cg_model_cfg* cfg, int B, int Tmax) {
@@ -1614,18 +1667,13 @@ extern "C" int cg_model_decode(cg_model* m, const int64_t* tok, int B, int pos, 
   if (carve_dec(&m->cfg, D, B, nullptr, W) > dec_ws_bytes) return CG_EINVAL;
   carve_dec(&m->cfg, D, B, (char*)dec_ws, W);
   const int d = D.d;
-  const float eps = m->cfg.ln_eps > 0 ? m->cfg.ln_eps : 1e-5f;
   const size_t es = C.dt == CG_BF16 ? 2 : 4;
   const size_t row = (size_t)2 * D.kvd * es;
   CK(cg_embed_fwd(tok, P(C, C.Lo.tok), C.Lo.pos >= 0 ? P(C, C.Lo.pos) + (size_t)pos * d : nullptr, W.x, B, 1, d, 0,
                   0.f, C.s));
   CK(cg_segstate_step(tok, B, m->cfg.sep_id, pos, segstate, C.s));
   for (int l = 0; l < D.L; ++l) {
-    const auto& o = C.Lo.lay[l];
-    CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, o.ln1w), P(C, o.ln1b), W.h, d, W.mean, W.rstd, B, d, eps, C.s));
-    cg_gemm_desc g = lin_fwd(C, W.h, d, o.wqkv, d, D.Nqkv, d, W.qkv, D.Nqkv);
-    g.epilogue = CG_EPI_BIAS; g.bias = P(C, o.bqkv);
-    CK(cg_gemm(&g, C.s));
+    CK(dec_ln1_qkv(C, W, l));
     if (D.rope)
       CK(cg_rope_tab(C.dt, W.qkv, D.Nqkv, B, 1, D.H, D.KV, D.hd, m->rope_cos + (size_t)pos * (D.hd / 2),
                      m->rope_sin + (size_t)pos * (D.hd / 2), 0, C.s));
@@ -1635,35 +1683,10 @@ extern "C" int cg_model_decode(cg_model* m, const int64_t* tok, int B, int pos, 
       return CG_ELAUNCH;
     CK(cg_attn_decode(C.dt, W.qkv, D.Nqkv, cl, 2 * D.kvd, Tmax, pos, m->cfg.sep_id >= 0 ? segstate : nullptr,
                       m->window, B, D.H, D.KV, D.hd, W.y, d, C.s));
-    g = lin_fwd(C, W.y, d, o.wp, d, d, d, W.xmid, d);
-    g.c_dtype = CG_F32;
-    g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.bp); g.resid = W.x; g.ldr = d;
-    CK(cg_gemm(&g, C.s));
-    CK(cg_layernorm_fwd(C.dt, W.xmid, d, P(C, o.ln2w), P(C, o.ln2b), W.h, d, W.mean, W.rstd, B, d, eps, C.s));
-    if (!D.swiglu) {
-      g = lin_fwd(C, W.h, d, o.w1, d, D.hid, d, W.g, D.hid);
-      g.epilogue = CG_EPI_BIAS | CG_EPI_GELU | CG_EPI_GELU_DERIV; g.bias = P(C, o.b1); g.aux_out = W.a; g.ld_aux = D.hid;
-      CK(cg_gemm(&g, C.s));
-      g = lin_fwd(C, W.g, D.hid, o.w2, D.hid, d, D.hid, W.x, d);
-      g.c_dtype = CG_F32;
-      g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.b2); g.resid = W.xmid; g.ldr = d;
-      CK(cg_gemm(&g, C.s));
-    } else {
-      g = lin_fwd(C, W.h, d, o.wgu, d, 2 * D.Hp, d, W.gu, 2 * D.Hp);
-      CK(cg_gemm(&g, C.s));
-      CK(cg_swiglu_fwd(C.dt, W.gu, 2 * D.Hp, D.Hp, W.s, D.Hp, B, D.hid, C.s));
-      g = lin_fwd(C, W.s, D.Hp, o.wd, D.Hp, d, D.Hp, W.x, d);
-      g.c_dtype = CG_F32;
-      g.epilogue = CG_EPI_RESID; g.resid = W.xmid; g.ldr = d;
-      CK(cg_gemm(&g, C.s));
-    }
+    CK(dec_proj_mlp(C, W, l));
   }
-  CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, C.Lo.lnfw), P(C, C.Lo.lnfb), W.xf, d, W.mean, W.rstd, B, d, eps, C.s));
-  const long long hoff = m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head;
-  cg_gemm_desc g = lin_fwd(C, W.xf, d, hoff, d, D.V, d, logits, D.V);
-  g.c_dtype = CG_F32;
-  CK(cg_gemm(&g, C.s));
-  return CG_OK;
+  CK(dec_ln_f(C, W));
+  return dec_head(C, W, logits);
 }
 
 // ===========================================================================
@@ -1724,52 +1747,23 @@ int decode_ragged_body(cg_model* m, const int64_t* tok, const int32_t* pos, int 
   if (carve_dec_ragged(&m->cfg, D, B, nullptr, W, lg) > dec_ws_bytes) return CG_EINVAL;
   carve_dec_ragged(&m->cfg, D, B, (char*)dec_ws, W, lg);
   const int d = D.d;
-  const float eps = m->cfg.ln_eps > 0 ? m->cfg.ln_eps : 1e-5f;
   const size_t es = C.dt == CG_BF16 ? 2 : 4;
   const size_t row = (size_t)2 * D.kvd * es;
   CK(cg_embed_fwd_pos(tok, P(C, C.Lo.tok), C.Lo.pos >= 0 ? P(C, C.Lo.pos) : nullptr, pos, W.x, B, d, D.V, Tmax, C.s));
   CK(cg_segstate_step_ragged(tok, pos, B, m->cfg.sep_id, Tmax, segstate, C.s));
   for (int l = 0; l < D.L; ++l) {
-    const auto& o = C.Lo.lay[l];
-    CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, o.ln1w), P(C, o.ln1b), W.h, d, W.mean, W.rstd, B, d, eps, C.s));
-    cg_gemm_desc g = lin_fwd(C, W.h, d, o.wqkv, d, D.Nqkv, d, W.qkv, D.Nqkv);
-    g.epilogue = CG_EPI_BIAS; g.bias = P(C, o.bqkv);
-    CK(cg_gemm(&g, C.s));
+    CK(dec_ln1_qkv(C, W, l));
     if (D.rope) CK(cg_rope_pos(C.dt, W.qkv, D.Nqkv, pos, B, D.H, D.KV, D.hd, m->rope_cos, m->rope_sin, Tmax, C.s));
     char* cl = (char*)cache + (size_t)l * B * Tmax * row;
     CK(cg_kv_append(C.dt, (const char*)W.qkv + (size_t)d * es, D.Nqkv, cl, 2 * D.kvd, Tmax, pos, B, 2 * D.kvd, C.s));
     CK(cg_attn_decode_ragged(C.dt, W.qkv, D.Nqkv, cl, 2 * D.kvd, Tmax, pos, m->cfg.sep_id >= 0 ? segstate : nullptr,
                              m->window, B, D.H, D.KV, D.hd, W.y, d, C.s));
-    g = lin_fwd(C, W.y, d, o.wp, d, d, d, W.xmid, d);
-    g.c_dtype = CG_F32;
-    g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.bp); g.resid = W.x; g.ldr = d;
-    CK(cg_gemm(&g, C.s));
-    CK(cg_layernorm_fwd(C.dt, W.xmid, d, P(C, o.ln2w), P(C, o.ln2b), W.h, d, W.mean, W.rstd, B, d, eps, C.s));
-    if (!D.swiglu) {
-      g = lin_fwd(C, W.h, d, o.w1, d, D.hid, d, W.g, D.hid);
-      g.epilogue = CG_EPI_BIAS | CG_EPI_GELU | CG_EPI_GELU_DERIV; g.bias = P(C, o.b1); g.aux_out = W.a; g.ld_aux = D.hid;
-      CK(cg_gemm(&g, C.s));
-      g = lin_fwd(C, W.g, D.hid, o.w2, D.hid, d, D.hid, W.x, d);
-      g.c_dtype = CG_F32;
-      g.epilogue = CG_EPI_BIAS | CG_EPI_RESID; g.bias = P(C, o.b2); g.resid = W.xmid; g.ldr = d;
-      CK(cg_gemm(&g, C.s));
-    } else {
-      g = lin_fwd(C, W.h, d, o.wgu, d, 2 * D.Hp, d, W.gu, 2 * D.Hp);
-      CK(cg_gemm(&g, C.s));
-      CK(cg_swiglu_fwd(C.dt, W.gu, 2 * D.Hp, D.Hp, W.s, D.Hp, B, D.hid, C.s));
-      g = lin_fwd(C, W.s, D.Hp, o.wd, D.Hp, d, D.Hp, W.x, d);
-      g.c_dtype = CG_F32;
-      g.epilogue = CG_EPI_RESID; g.resid = W.xmid; g.ldr = d;
-      CK(cg_gemm(&g, C.s));
-    }
+    CK(dec_proj_mlp(C, W, l));
   }
-  CK(cg_layernorm_fwd(C.dt, W.x, d, P(C, C.Lo.lnfw), P(C, C.Lo.lnfb), W.xf, d, W.mean, W.rstd, B, d, eps, C.s));
+  CK(dec_ln_f(C, W));
   // the ln_f history: the active rows' new ln_f output -> hist[b][pos[b]]
   if (hist) CK(cg_kv_append(C.dt, W.xf, d, hist, d, Tmax, pos, B, d, C.s));
-  const long long hoff = m->cfg.tie_embeddings ? C.Lo.tok : C.Lo.head;
-  cg_gemm_desc g = lin_fwd(C, W.xf, d, hoff, d, D.V, d, lg, D.V);
-  g.c_dtype = CG_F32;
-  CK(cg_gemm(&g, C.s));
+  CK(dec_head(C, W, lg));
   CK(cg_gather_rows(lg, D.V, pos, 0, Tmax, logits, D.V, D.V, nullptr, nullptr, B, C.s));
   if (term_logits)
     CK(cg_row_head(C.dt, W.xf, d, P(C, C.Lo.termw), P(C, C.Lo.termb), pos, Tmax, B, d, nc, term_logits, ld_term, C.s));

@@ -13,28 +13,6 @@ __device__ __forceinline__ bool row_active(const int32_t* __restrict__ pos, int 
   return p >= 0 && p < Tmax;
 }
 
-// 16 bytes of a row as floats: EPL = 8 bf16 or 4 fp32 elements per lane
-template <typename T_> struct Chunk;
-template <> struct Chunk<float> {
-  static constexpr int EPL = 4;
-  static __device__ __forceinline__ void load(const float* p, float* v) {
-    const float4 a = *(const float4*)p;
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  }
-};
-template <> struct Chunk<bf16_t> {
-  static constexpr int EPL = 8;
-  static __device__ __forceinline__ void load(const bf16_t* p, float* v) {
-    const uint4 a = *(const uint4*)p;
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(w[j] << 16);
-      v[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-    }
-  }
-};
-
 // sum over the lpr (2 / 4 / 8 / 16, a power of two) adjacent lanes of a key row, all in DPP (the
 // steps of wave_reduce that stay inside a 16-lane row); every lane of the group gets the total
 __device__ __forceinline__ float group_sum(float v, int lpr) {
@@ -63,7 +41,7 @@ __global__ __launch_bounds__(64 * DR_WAVES) void attn_decode_ragged_kernel(
     const T_* __restrict__ q, long long ldq, const T_* __restrict__ cache, long long ldc, int Tmax,
     const int32_t* __restrict__ pos, const int32_t* __restrict__ seg, int window, int H, int KV, int hd, int lpr,
     float scale, T_* __restrict__ y, long long ldy) {
-  constexpr int EPL = Chunk<T_>::EPL;
+  constexpr int EPL = 16 / sizeof(T_);  // 16 bytes of a row per lane: 8 bf16 or 4 fp32 elements
   __shared__ float sm[DR_WAVES][DR_GC], sl[DR_WAVES][DR_GC];
   __shared__ float sacc[DR_WAVES][DR_GC][64];
   const int kvh = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -90,7 +68,7 @@ __global__ __launch_bounds__(64 * DR_WAVES) void attn_decode_ragged_kernel(
 #pragma unroll
       for (int e = 0; e < EPL; ++e) { qv[g][e] = 0.f; acc[g][e] = 0.f; }
       if (g < ng && col_ok) {
-        Chunk<T_>::load(q + (long long)b * ldq + (long long)(kvh * G + g0 + g) * hd + c * EPL, qv[g]);
+        ld_vec<EPL>(q + (long long)b * ldq + (long long)(kvh * G + g0 + g) * hd + c * EPL, qv[g]);
 #pragma unroll
         for (int e = 0; e < EPL; ++e) qv[g][e] *= scale;
       }
@@ -104,8 +82,8 @@ __global__ __launch_bounds__(64 * DR_WAVES) void attn_decode_ragged_kernel(
 #pragma unroll
       for (int e = 0; e < EPL; ++e) { kx[e] = 0.f; vx[e] = 0.f; }
       if (valid && col_ok) {
-        Chunk<T_>::load(kb + (long long)j * ldc, kx);
-        Chunk<T_>::load(vb + (long long)j * ldc, vx);
+        ld_vec<EPL>(kb + (long long)j * ldc, kx);
+        ld_vec<EPL>(vb + (long long)j * ldc, vx);
       }
 #pragma unroll
       for (int g = 0; g < DR_GC; ++g) {

@@ -26,28 +26,6 @@
 namespace {
 constexpr int OP_LDS_MAX = 160 * 1024;
 
-// 16 bytes of a row as floats
-template <typename T_> struct Row16;
-template <> struct Row16<float> {
-  static constexpr int EPL = 4;
-  static __device__ __forceinline__ void load(const float* p, float* v) {
-    const float4 a = *(const float4*)p;
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  }
-};
-template <> struct Row16<bf16_t> {
-  static constexpr int EPL = 8;
-  static __device__ __forceinline__ void load(const bf16_t* p, float* v) {
-    const uint4 a = *(const uint4*)p;
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(w[j] << 16);
-      v[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-    }
-  }
-};
-
 // the history row the pair (row at position p, head i) reads, or -1
 __device__ __forceinline__ int pair_src(const cg_offprior_args& a, int p, int i) {
   if (p < 0 || p >= a.Tmax || a.weight[i] == 0.f || a.offset[i] < 1) return -1;
@@ -60,7 +38,7 @@ __device__ __forceinline__ int pair_src(const cg_offprior_args& a, int p, int i)
 // (head, XK-chunk) pair, and the loads of step s + 1 are issued before the FMAs of step s.
 template <typename T_, int STAGE, int TN, int XK>
 __global__ __launch_bounds__(256) void offset_prior_kernel(cg_offprior_args a, int kw, int kwp, int vec) {
-  constexpr int EPL = Row16<T_>::EPL;
+  constexpr int EPL = 16 / sizeof(T_);  // 16 bytes of a row as floats
   constexpr int NO = TN * 64 / 256;  // outputs a thread finishes
   extern __shared__ __attribute__((aligned(16))) float op_smem[];
   float* Ws = op_smem;                   // [TN][4 waves][kwp], zero beyond the N columns and the d elements
@@ -110,7 +88,7 @@ __global__ __launch_bounds__(256) void offset_prior_kernel(cg_offprior_args a, i
           const int k = k0 + kc + j;
           const bool in = k + EPL <= kend;
           float v[EPL];
-          Row16<T_>::load(x + (in ? k : 0), v);
+          ld_vec<EPL>(x + (in ? k : 0), v);
 #pragma unroll
           for (int e = 0; e < EPL; ++e) xr[j + e] = in ? v[e] : 0.f;
         }
@@ -137,7 +115,7 @@ __global__ __launch_bounds__(256) void offset_prior_kernel(cg_offprior_args a, i
       for (int u = 0; u < QMAX; ++u) {  // (no branch: a group past the slice reads the slice's first instead)
         const int q = q0 + tid + 256 * u;
         const bool in = q < ngroup && n0 + q / gpr < N;
-        Row16<T_>::load(w + (in ? (long long)(n0 + q / gpr) * d + (q % gpr) * EPL : (long long)n0 * d), v[u]);
+        ld_vec<EPL>(w + (in ? (long long)(n0 + q / gpr) * d + (q % gpr) * EPL : (long long)n0 * d), v[u]);
       }
 #pragma unroll
       for (int u = 0; u < QMAX; ++u) {
@@ -229,7 +207,7 @@ __global__ __launch_bounds__(256) void offset_prior_kernel(cg_offprior_args a, i
 
 template <typename T_, int STAGE, int TN, int XK>
 int launch_stage_xk(const cg_offprior_args& a, int kw, hipStream_t s) {
-  constexpr int EPL = Row16<T_>::EPL;
+  constexpr int EPL = 16 / sizeof(T_);  // 16 bytes of a row as floats
   const int N = STAGE == 3 ? a.V : a.d;
   const int kwp = (kw + XK - 1) / XK * XK;
   const size_t lds = ((size_t)TN * 4 * kwp + 4 * TN * 64) * sizeof(float);

@@ -53,37 +53,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 
 // Vectorised fast path: cols = 64*W*NV, each lane owns NV runs of W consecutive columns at
 // W*(lane + 64 i) (every wave-instruction moves 64*W contiguous elements; W = 4 -> 1 KiB of
-// fp32 x per wave-instruction, W = 2 for widths that are not a multiple of 256).
-template <int W>
-__device__ __forceinline__ void ldw(const float* p, float* v) {
-  if constexpr (W == 4) {
-    const float4 a = *(const float4*)p;
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-    const float2 a = *(const float2*)p;
-    v[0] = a.x; v[1] = a.y;
-  }
-}
-template <int W>
-__device__ __forceinline__ void ldw(const bf16_t* p, float* v) {
-  uint32_t u[W / 2];
-  if constexpr (W == 4) {
-    const uint2 t = *(const uint2*)p;
-    u[0] = t.x; u[1] = t.y;
-  } else {
-    u[0] = *(const uint32_t*)p;
-  }
-#pragma unroll
-  for (int j = 0; j < W / 2; ++j) {
-    v[2 * j] = __uint_as_float(u[j] << 16);
-    v[2 * j + 1] = __uint_as_float(u[j] & 0xFFFF0000u);
-  }
-}
-template <int W>
-__device__ __forceinline__ void stw(float* p, const float* v) {
-  if constexpr (W == 4) *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-  else *(float2*)p = make_float2(v[0], v[1]);
-}
+// fp32 x per wave-instruction, W = 2 for widths that are not a multiple of 256): ld_vec<W> /
+// st_vec<W> of common.h.
 // the residual-gradient row: read again only by the next LayerNorm backward, several kernels
 // later, so it is stored nontemporal (round 5, same-box A/B of the C4 step: 14.57 -> 14.50 ms,
 // profiles/round5/nt_stores_ab.txt)
@@ -96,14 +67,6 @@ __device__ __forceinline__ void stw_g(float* p, const float* v) {
     typedef float f2_nt __attribute__((ext_vector_type(2)));
     __builtin_nontemporal_store((f2_nt){v[0], v[1]}, (f2_nt*)p);
   }
-}
-template <int W>
-__device__ __forceinline__ void stw(bf16_t* p, const float* v) {
-  uint32_t u[W / 2];
-#pragma unroll
-  for (int j = 0; j < W / 2; ++j) u[j] = (uint32_t)f2bf(v[2 * j]) | ((uint32_t)f2bf(v[2 * j + 1]) << 16);
-  if constexpr (W == 4) *(uint2*)p = make_uint2(u[0], u[1]);
-  else *(uint32_t*)p = u[0];
 }
 
 // LayerNorm row prefetch: the backward keeps two rows in flight per wave; the forward runs 4 rows
@@ -128,15 +91,15 @@ __global__ __launch_bounds__(256) void ln_fwd_pf(const float* __restrict__ x, lo
   float gm[NV][W], bt[NV][W], v[NV][W];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    ldw<W>(gamma + W * (lane + 64 * i), gm[i]);
-    ldw<W>(beta + W * (lane + 64 * i), bt[i]);
-    ldw<W>(x + (long long)r0 * ldx + W * (lane + 64 * i), v[i]);
+    ld_vec<W>(gamma + W * (lane + 64 * i), gm[i]);
+    ld_vec<W>(beta + W * (lane + 64 * i), bt[i]);
+    ld_vec<W>(x + (long long)r0 * ldx + W * (lane + 64 * i), v[i]);
   }
   for (int row = r0; row < r1; ++row) {
     float nv[NV][W];
     const int nr = min(row + 1, r1 - 1);  // the last row's reload is unused
 #pragma unroll
-    for (int i = 0; i < NV; ++i) ldw<W>(x + (long long)nr * ldx + W * (lane + 64 * i), nv[i]);
+    for (int i = 0; i < NV; ++i) ld_vec<W>(x + (long long)nr * ldx + W * (lane + 64 * i), nv[i]);
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -158,7 +121,7 @@ __global__ __launch_bounds__(256) void ln_fwd_pf(const float* __restrict__ x, lo
       float o[W];
 #pragma unroll
       for (int j = 0; j < W; ++j) o[j] = (v[i][j] - mu) * rs * gm[i][j] + bt[i][j];
-      stw<W>(yr + W * (lane + 64 * i), o);
+      st_vec<W>(yr + W * (lane + 64 * i), o);
     }
     if (lane == 0) {
       if (mean) mean[row] = mu;
@@ -183,7 +146,7 @@ __device__ __forceinline__ void ln_fwd_row(const float* __restrict__ x, long lon
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    ldw<W>(xr + W * (lane + 64 * i), v[i]);
+    ld_vec<W>(xr + W * (lane + 64 * i), v[i]);
 #pragma unroll
     for (int j = 0; j < W; ++j) s += v[i][j];
   }
@@ -202,11 +165,11 @@ __device__ __forceinline__ void ln_fwd_row(const float* __restrict__ x, long lon
   for (int i = 0; i < NV; ++i) {
     const int c = W * (lane + 64 * i);
     float gm[W], bt[W], o[W];
-    ldw<W>(gamma + c, gm);
-    ldw<W>(beta + c, bt);
+    ld_vec<W>(gamma + c, gm);
+    ld_vec<W>(beta + c, bt);
 #pragma unroll
     for (int j = 0; j < W; ++j) o[j] = (v[i][j] - mu) * rs * gm[j] + bt[j];
-    stw<W>(yr + c, o);
+    st_vec<W>(yr + c, o);
   }
   if (lane == 0) {
     if (mean) mean[row] = mu;
@@ -396,7 +359,7 @@ __global__ __launch_bounds__(256) void ln_bwd_vec(const TD* __restrict__ dy, lon
   float gm[NV][W], dg[NV][W], db[NV][W], dc[NV][W];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    ldw<W>(gamma + W * (lane + 64 * i), gm[i]);
+    ld_vec<W>(gamma + W * (lane + 64 * i), gm[i]);
 #pragma unroll
     for (int j = 0; j < W; ++j) dg[i][j] = db[i][j] = dc[i][j] = 0.f;
   }
@@ -407,13 +370,13 @@ __global__ __launch_bounds__(256) void ln_bwd_vec(const TD* __restrict__ dy, lon
     in.rs = rstd[row];
     if (g_in) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) ldw<W>(g_in + (long long)row * cols + W * (lane + 64 * i), in.g2[i]);
+      for (int i = 0; i < NV; ++i) ld_vec<W>(g_in + (long long)row * cols + W * (lane + 64 * i), in.g2[i]);
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = W * (lane + 64 * i);
-      ldw<W>(dy + (long long)row * lddy + c, in.d[i]);
-      ldw<W>(x + (long long)row * ldx + c, in.xv[i]);
+      ld_vec<W>(dy + (long long)row * lddy + c, in.d[i]);
+      ld_vec<W>(x + (long long)row * ldx + c, in.xv[i]);
     }
   };
   RowIn cur;
@@ -467,7 +430,7 @@ __global__ __launch_bounds__(256) void ln_bwd_vec(const TD* __restrict__ dy, lon
             o[j + 1] = (h >> 16) >= thr ? o[j + 1] * dscale : 0.f;
           }
         }
-        stw<W>(g_out_t + (long long)row * cols + c, o);
+        st_vec<W>(g_out_t + (long long)row * cols + c, o);
 #pragma unroll
         for (int j = 0; j < W; ++j) dc[i][j] += o[j];  // column sum of the consumer's dY (its bias gradient)
       }
@@ -477,9 +440,9 @@ __global__ __launch_bounds__(256) void ln_bwd_vec(const TD* __restrict__ dy, lon
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = W * (lane + 64 * i);
-    stw<W>(&red[wave][c], dg[i]);
-    stw<W>(&red[wave][cols + c], db[i]);
-    stw<W>(&red[wave][2 * cols + c], dc[i]);
+    st_vec<W>(&red[wave][c], dg[i]);
+    st_vec<W>(&red[wave][cols + c], db[i]);
+    st_vec<W>(&red[wave][2 * cols + c], dc[i]);
   }
   __syncthreads();
   const int nw = (want_col ? 3 : 2);
@@ -1122,36 +1085,9 @@ __global__ __launch_bounds__(256) void rope_kernel(T_* __restrict__ qkv, long lo
 
 // Vectorised forms (8 consecutive elements per thread: 16-B bf16 / 2x16-B fp32 accesses, one
 // 32-bit row division per 8 elements instead of 64-bit divisions per element) -- the scalar
-// kernels above ran at 2.5-4 TB/s on C3 (d384, hd48), these are HBM-bound.
-template <typename T_> __device__ __forceinline__ void ld8(const T_* p, float* v);
-template <> __device__ __forceinline__ void ld8<float>(const float* p, float* v) {
-  const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <> __device__ __forceinline__ void ld8<bf16_t>(const bf16_t* p, float* v) {
-  const uint4 a = *(const uint4*)p;
-  const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(w[j] << 16);
-    v[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-  }
-}
-template <typename T_> __device__ __forceinline__ void st8(T_* p, const float* v);
-template <> __device__ __forceinline__ void st8<float>(float* p, const float* v) {
-  ((float4*)p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-  ((float4*)p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
-template <> __device__ __forceinline__ void st8<bf16_t>(bf16_t* p, const float* v) {
-  uint32_t w[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) w[j] = (uint32_t)f2bf(v[2 * j]) | ((uint32_t)f2bf(v[2 * j + 1]) << 16);
-  *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-}
-// 8-element runs usable: every row start 16-B aligned and the run length a multiple of 8
-static inline bool vec8_ok(int es, const void* p, long long ld) {
-  return ((uintptr_t)p % 16) == 0 && (ld * es) % 16 == 0;
-}
+// kernels above ran at 2.5-4 TB/s on C3 (d384, hd48), these are HBM-bound.  ld_vec<8> / st_vec<8>
+// of common.h; 8-element runs are usable where every row start is 16-B aligned (cg_rows16) and
+// the run length is a multiple of 8.
 
 // rotate-half RoPE, one thread = 8 consecutive i of one (row, head) and their partners i + half
 template <typename T_>
@@ -1166,17 +1102,17 @@ __global__ __launch_bounds__(256) void rope_vec_kernel(T_* __restrict__ qkv, lon
     const int t = m % T;
     T_* base = qkv + (long long)m * ld + (long long)h * hd;
     float x1[8], x2[8], cs[8], sn[8], y1[8], y2[8];
-    ld8<T_>(base + i, x1);
-    ld8<T_>(base + i + half, x2);
-    ld8<float>(cosb + (long long)t * half + i, cs);
-    ld8<float>(sinb + (long long)t * half + i, sn);
+    ld_vec<8>(base + i, x1);
+    ld_vec<8>(base + i + half, x2);
+    ld_vec<8>(cosb + (long long)t * half + i, cs);
+    ld_vec<8>(sinb + (long long)t * half + i, sn);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (!inverse) { y1[k] = x1[k] * cs[k] - x2[k] * sn[k]; y2[k] = x2[k] * cs[k] + x1[k] * sn[k]; }
       else          { y1[k] = x1[k] * cs[k] + x2[k] * sn[k]; y2[k] = x2[k] * cs[k] - x1[k] * sn[k]; }
     }
-    st8<T_>(base + i, y1);
-    st8<T_>(base + i + half, y2);
+    st_vec<8>(base + i, y1);
+    st_vec<8>(base + i + half, y2);
   }
 }
 
@@ -1187,7 +1123,7 @@ extern "C" int cg_rope_tab(int dtype, void* qkv, long long ldqkv, int B, int T, 
   const long long total = (long long)rows * nh * (hd / 2);
   if (total == 0) return CG_OK;
   const int es = dtype == CG_BF16 ? 2 : 4;
-  if ((hd / 2) % 8 == 0 && vec8_ok(es, qkv, ldqkv) && ((uintptr_t)cos_tab | (uintptr_t)sin_tab) % 16 == 0 &&
+  if ((hd / 2) % 8 == 0 && cg_rows16(qkv, ldqkv, es) && ((uintptr_t)cos_tab | (uintptr_t)sin_tab) % 16 == 0 &&
       total / 8 < (1LL << 31)) {
     int vb = (int)((total / 8 + 255) / 256);
     if (vb > 16384) vb = 16384;
@@ -1259,11 +1195,11 @@ __global__ __launch_bounds__(256) void swiglu_fwd_vec_kernel(const T_* __restric
   for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
     const int m = e / cpr, j = 8 * (e - m * cpr);
     float g[8], u[8], v[8];
-    ld8<T_>(gu + (long long)m * ldgu + j, g);
-    ld8<T_>(gu + (long long)m * ldgu + Hp + j, u);
+    ld_vec<8>(gu + (long long)m * ldgu + j, g);
+    ld_vec<8>(gu + (long long)m * ldgu + Hp + j, u);
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = j + k < H ? silu_f(g[k]) * u[k] : 0.f;
-    st8<T_>(s + (long long)m * lds + j, v);
+    st_vec<8>(s + (long long)m * lds + j, v);
   }
 }
 template <typename T_>
@@ -1274,9 +1210,9 @@ __global__ __launch_bounds__(256) void swiglu_bwd_vec_kernel(const T_* __restric
   for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
     const int m = e / cpr, j = 8 * (e - m * cpr);
     float g[8], u[8], d[8], dg[8], du[8];
-    ld8<T_>(gu + (long long)m * ldgu + j, g);
-    ld8<T_>(gu + (long long)m * ldgu + Hp + j, u);
-    ld8<T_>(ds + (long long)m * ldds + j, d);
+    ld_vec<8>(gu + (long long)m * ldgu + j, g);
+    ld_vec<8>(gu + (long long)m * ldgu + Hp + j, u);
+    ld_vec<8>(ds + (long long)m * ldds + j, d);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       dg[k] = du[k] = 0.f;
@@ -1287,21 +1223,18 @@ __global__ __launch_bounds__(256) void swiglu_bwd_vec_kernel(const T_* __restric
         dg[k] = d[k] * u[k] * sg * (1.0f + g[k] * (1.0f - sg));
       }
     }
-    st8<T_>(dgu + (long long)m * lddgu + j, dg);
-    st8<T_>(dgu + (long long)m * lddgu + Hp + j, du);
+    st_vec<8>(dgu + (long long)m * lddgu + j, dg);
+    st_vec<8>(dgu + (long long)m * lddgu + Hp + j, du);
   }
 }
-static inline int vec_blocks(long long chunks) {
-  const long long b = (chunks + 255) / 256;
-  return (int)(b > 16384 ? 16384 : b);
-}
+static inline int vec_blocks(long long chunks) { return cg_grid_cap((chunks + 255) / 256, 16384); }
 
 extern "C" int cg_swiglu_fwd(int dtype, const void* gu, long long ldgu, int Hp, void* s, long long lds, int rows,
                              int H, void* stream) {
   const long long total = (long long)rows * Hp;
   if (total == 0) return CG_OK;
   const int es = dtype == CG_BF16 ? 2 : 4;
-  if (Hp % 8 == 0 && vec8_ok(es, gu, ldgu) && vec8_ok(es, s, lds) && total / 8 < (1LL << 31)) {
+  if (Hp % 8 == 0 && cg_rows16(gu, ldgu, es) && cg_rows16(s, lds, es) && total / 8 < (1LL << 31)) {
     if (dtype == CG_BF16)
       hipLaunchKernelGGL(swiglu_fwd_vec_kernel<bf16_t>, dim3(vec_blocks(total / 8)), dim3(256), 0,
                          (hipStream_t)stream, (const bf16_t*)gu, ldgu, Hp, (bf16_t*)s, lds, rows, H);
@@ -1327,7 +1260,7 @@ extern "C" int cg_swiglu_bwd(int dtype, const void* gu, long long ldgu, int Hp, 
   const long long total = (long long)rows * Hp;
   if (total == 0) return CG_OK;
   const int es = dtype == CG_BF16 ? 2 : 4;
-  if (Hp % 8 == 0 && vec8_ok(es, gu, ldgu) && vec8_ok(es, ds, ldds) && vec8_ok(es, dgu, lddgu) &&
+  if (Hp % 8 == 0 && cg_rows16(gu, ldgu, es) && cg_rows16(ds, ldds, es) && cg_rows16(dgu, lddgu, es) &&
       total / 8 < (1LL << 31)) {
     if (dtype == CG_BF16)
       hipLaunchKernelGGL(swiglu_bwd_vec_kernel<bf16_t>, dim3(vec_blocks(total / 8)), dim3(256), 0,
@@ -1536,30 +1469,11 @@ __global__ __launch_bounds__(1024) void ce_denom_kernel(const int64_t* __restric
     const int64_t t = tg[r];
     if (t != ignore) s4[0] += w ? w[t] : 1.0f;
   }
-  red[threadIdx.x] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_1024((s4[0] + s4[1]) + (s4[2] + s4[3]), red);
   if (threadIdx.x == 0) ws[0] = red[0];
 }
 
-// SPLIT (dtype CG_BF16X2): g is stored as bf16 hi = bf16(g) at column c and bf16 lo =
-// bf16(g - hi) at column ldd/2 + c, so a bf16 MFMA product over [hi | lo] x [W; W] sees g to
-// ~16 significant bits (the tied-head dX product feeds ln_f's bias gradient, a column sum
-// over all tokens that cancels to a small value: 8-bit dlogits leave ~10% error in it).
-template <typename TD, bool SPLIT = false>
-__device__ __forceinline__ void st_grad(TD* dr, int c, long long half, float g) {
-  if constexpr (SPLIT) {
-    const bf16_t hi = f2bf(g);
-    dr[c] = hi;
-    dr[half + c] = f2bf(g - bf2f(hi));
-  } else {
-    st_act<TD>(dr + c, g);
-  }
-}
-
+// (dlogits element layouts: st_grad of common.h)
 template <typename TD, bool SPLIT = false>
 __global__ __launch_bounds__(256) void ce_main_kernel(const float* __restrict__ logits, long long ldl,
                                                       const int64_t* __restrict__ tg, int rows, int V, float eps,
@@ -1624,19 +1538,11 @@ __global__ __launch_bounds__(1024) void ce_final_kernel(const float* __restrict_
   __shared__ float red[1024];
   float s = 0.f;
   for (int b = threadIdx.x; b < nblk; b += 1024) s += ws[1 + b];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_1024(s, red);
   if (threadIdx.x == 0) *loss = red[0] / ws[0];
 }
 
-static int ce_blocks(int rows) {
-  int b = cg_cdiv(rows, 4);
-  return b > CE_BLK ? CE_BLK : (b < 1 ? 1 : b);
-}
+static int ce_blocks(int rows) { return cg_grid_cap(cg_cdiv(rows, 4), CE_BLK); }
 extern "C" size_t cg_ce_workspace(int rows) { return (size_t)(1 + ce_blocks(rows)) * sizeof(float); }
 
 extern "C" int cg_cross_entropy(const float* logits, long long ldl, const int64_t* targets, int rows, int V,
@@ -1944,13 +1850,10 @@ extern "C" int cg_gather_sequences(int elem_bytes, const void* flat, const int64
 // 2 state at position (#non-PAD - 1).  One thread per (sequence, feature); the token ids of a
 // row are read once per wave from L1/L2, the states coalesced along the feature axis.
 // ===========================================================================
-struct TokMask {
-  uint32_t w[8];  // ids 0..255
-};
 template <typename T_>
 __global__ __launch_bounds__(256) void pool_hidden_kernel(const T_* __restrict__ h, long long ldh,
                                                           const int64_t* __restrict__ idx, int T, int d, int pad,
-                                                          int mode, TokMask cm, float* __restrict__ out) {
+                                                          int mode, cg_id_mask cm, float* __restrict__ out) {
   const int b = blockIdx.y;
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= d) return;
@@ -1966,12 +1869,7 @@ __global__ __launch_bounds__(256) void pool_hidden_kernel(const T_* __restrict__
   float s = 0.f, cnt = 0.f;
   for (int t = 0; t < T; ++t) {
     const int64_t v = row[t];
-    bool w;
-    if (mode == 0)
-      w = v != pad;
-    else
-      w = v >= 0 && v < 256 && ((cm.w[v >> 5] >> (v & 31)) & 1u);
-    if (w) {
+    if (mode == 0 ? v != pad : cg_mask_has(cm, v)) {
       s += ld_act<T_>(hb + (long long)t * ldh);
       cnt += 1.f;
     }
@@ -1983,8 +1881,8 @@ extern "C" int cg_pool_hidden(int dtype, const void* h, long long ldh, const int
   if (B < 0 || T < 0 || d < 0 || ldh < d || mode < 0 || mode > 2) return CG_EINVAL;
   if ((long long)B * d == 0) return CG_OK;
   if (!h || !idx || !out || (mode == 1 && !content_mask)) return CG_EINVAL;
-  TokMask cm;
-  for (int i = 0; i < 8; ++i) cm.w[i] = content_mask ? content_mask[i] : 0u;
+  cg_id_mask cm = {};
+  cg_mask_fill(cm, content_mask);  // NULL (modes 0 and 2 never read it): the empty set
   const dim3 g(cg_cdiv(d, 256), B);
   if (dtype == CG_BF16)
     hipLaunchKernelGGL(pool_hidden_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)h, ldh, idx, T,

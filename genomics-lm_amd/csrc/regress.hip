@@ -127,8 +127,7 @@ __global__ __launch_bounds__(1024) void gram_count_kernel(const int32_t* __restr
   const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int n = 0;
   for (long long r = threadIdx.x; r < rows; r += 1024) n += grp[r] == g;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) n += __shfl_xor(n, o);
+  n = wave_sum(n);
   if (lane == 0) wc[wave] = n;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -289,7 +288,6 @@ __global__ __launch_bounds__(256) void gram_final_kernel(const double* __restric
   *o = accumulate ? *o + sum : sum;
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct GramLayout {
   size_t cnt, off, perm, part, total;
   int nb, npair, S;
@@ -307,9 +305,9 @@ inline GramLayout gram_layout(long long rows, int P, int G) {
   if (S < 1) S = 1;
   L.S = (int)S;
   L.cnt = 0;
-  L.off = up256((size_t)G * sizeof(int32_t));
-  L.perm = L.off + up256((size_t)G * sizeof(int32_t));
-  L.part = L.perm + up256((size_t)rows * sizeof(int32_t));
+  L.off = cg_rup((size_t)G * sizeof(int32_t), 256);
+  L.perm = L.off + cg_rup((size_t)G * sizeof(int32_t), 256);
+  L.part = L.perm + cg_rup((size_t)rows * sizeof(int32_t), 256);
   L.total = L.part + (size_t)G * L.S * L.npair * GR_BLK * GR_BLK * sizeof(double);
   return L;
 }

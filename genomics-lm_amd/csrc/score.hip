@@ -12,70 +12,6 @@ constexpr int SC_V = 1024;      // widest vocabulary (16 chunks of 64 columns pe
 constexpr int SC_WAVES = 4;     // rows per workgroup pass
 constexpr int SC_BLK = 4096;    // grid cap; rows beyond 4 * SC_BLK are grid-strided
 
-// the wave_reduce of common.h for any 4- or 8-byte value: the same six exchange steps (DPP inside
-// the 16-lane rows, then the two permlane swaps), each moving the value's 32-bit words
-template <int STEP>
-__device__ __forceinline__ uint32_t dpp_word(uint32_t v) {
-  constexpr int ctrl = STEP == 0 ? 0xB1 : STEP == 1 ? 0x4E : STEP == 2 ? 0x141 : 0x140;
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, ctrl, 0xF, 0xF, false);
-}
-template <typename T> struct Words;
-template <> struct Words<int> {
-  template <int STEP> static __device__ __forceinline__ int dpp(int v) { return (int)dpp_word<STEP>((uint32_t)v); }
-  template <bool WIDE> static __device__ __forceinline__ void swap(int v, int& a, int& b) {
-    if constexpr (WIDE) {
-      const auto r = __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
-      a = (int)r[0]; b = (int)r[1];
-    } else {
-      const auto r = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
-      a = (int)r[0]; b = (int)r[1];
-    }
-  }
-};
-template <> struct Words<double> {
-  static __device__ __forceinline__ double join(uint32_t lo, uint32_t hi) {
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-  }
-  template <int STEP> static __device__ __forceinline__ double dpp(double v) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return join(dpp_word<STEP>((uint32_t)u), dpp_word<STEP>((uint32_t)(u >> 32)));
-  }
-  template <bool WIDE> static __device__ __forceinline__ void swap(double v, double& a, double& b) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
-    if constexpr (WIDE) {
-      const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-      const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-      a = join(rl[0], rh[0]); b = join(rl[1], rh[1]);
-    } else {
-      const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-      const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-      a = join(rl[0], rh[0]); b = join(rl[1], rh[1]);
-    }
-  }
-};
-template <typename T, typename F>
-__device__ __forceinline__ T wave_reduce_t(T v, F op) {
-  v = op(v, Words<T>::template dpp<0>(v));
-  v = op(v, Words<T>::template dpp<1>(v));
-  v = op(v, Words<T>::template dpp<2>(v));
-  v = op(v, Words<T>::template dpp<3>(v));
-  T a, b;
-  Words<T>::template swap<false>(v, a, b);
-  v = op(a, b);
-  Words<T>::template swap<true>(v, a, b);
-  return op(a, b);
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-  return wave_reduce_t<double>(v, [](double a, double b) { return a + b; });
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-  return wave_reduce_t<int>(v, [](int a, int b) { return a + b; });
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-  return wave_reduce_t<int>(v, [](int a, int b) { return a < b ? a : b; });
-}
-
 struct ScoreArgs {
   const float* logits; long long ldl;
   const int64_t* targets;
@@ -111,7 +47,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_rows_kernel(ScoreArgs A) 
     for (int k = 1; k < NCH; ++k)
       if (z[k] > mloc) { mloc = z[k]; iloc = lane + 64 * k; }
     const float mx = wave_max(mloc);
-    const int amax = wave_min_i(mloc == mx ? iloc : INT_MAX);
+    const int amax = wave_min(mloc == mx ? iloc : INT_MAX);
     // s1 = sum over c != argmax of exp(z - max) (the argmax term is exactly 1) and, for the
     // entropy, sum exp(z - max) (max - z): fp64 sums of non-negative terms, so log1p(s1) = lse - max
     // and everything built from it keep full relative accuracy however peaked the row is
@@ -127,15 +63,15 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_rows_kernel(ScoreArgs A) 
         if (e > 0.0) sez += e * dz;  // p == 0 (z = -inf) adds 0, never 0 * inf
       }
     }
-    s1 = wave_sum_d(s1);
-    if (want_ent) sez = wave_sum_d(sez);
+    s1 = wave_sum(s1);
+    if (want_ent) sez = wave_sum(sez);
     const double lgs = log1p(s1);
     const double lse = m + lgs;
     if (want_smooth) {
 #pragma unroll
       for (int k = 0; k < NCH; ++k)
         if (lane + 64 * k < V) ssm += lse - (double)z[k];
-      ssm = wave_sum_d(ssm);
+      ssm = wave_sum(ssm);
     }
     // the target
     long long y = -1;
@@ -156,7 +92,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_rows_kernel(ScoreArgs A) 
           const int c = lane + 64 * k;
           if (c < V && (z[k] > zy || (z[k] == zy && c < y))) ++cnt;
         }
-        rk = wave_sum_i(cnt);
+        rk = wave_sum(cnt);
       }
       const double nll = -lp;
       a_nll += nll;
@@ -204,12 +140,7 @@ __global__ __launch_bounds__(1024) void score_final_kernel(const double* __restr
   for (int q = 0; q < 4; ++q) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nblk; b += 1024) s += part[(long long)b * 4 + q];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-      if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
+    block_sum_1024(s, red);
     if (threadIdx.x == 0) acc[q] += red[0];
     __syncthreads();
   }
@@ -233,18 +164,15 @@ __global__ __launch_bounds__(64) void score_seq_kernel(const double* __restrict_
       n += (y != ignore && y >= 0 && y < V) ? 1 : 0;
     }
   }
-  s = wave_sum_d(s);
-  n = wave_sum_i(n);
+  s = wave_sum(s);
+  n = wave_sum(n);
   if (lane == 0) {
     if (seq_logp) seq_logp[b] = s;
     if (seq_count) seq_count[b] = n;
   }
 }
 
-int score_blocks(int rows) {
-  const int b = cg_cdiv(rows, SC_WAVES);
-  return b > SC_BLK ? SC_BLK : (b < 1 ? 1 : b);
-}
+int score_blocks(int rows) { return cg_grid_cap(cg_cdiv(rows, SC_WAVES), SC_BLK); }
 // [4 * blocks] fp64 partials, then one fp64 per row
 size_t score_part_bytes(int rows) { return (size_t)score_blocks(rows) * 4 * sizeof(double); }
 }  // namespace

@@ -21,24 +21,6 @@ constexpr int TC_ROWS = 64;    // rows per chunk = lanes per wave
 constexpr int TC_COLS = 256;   // columns per backward wave (4 per lane)
 constexpr int TC_MAXC = 16;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
-// four adjacent activations, widened exactly
-__device__ __forceinline__ float4 ld_act4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ float4 ld_act4(const bf16_t* p) {
-  const uint2 v = *(const uint2*)p;
-  return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u), __uint_as_float(v.y << 16),
-                     __uint_as_float(v.y & 0xFFFF0000u));
-}
-
 // the lane's label: y in [0, C) and its class weight, or y = -1 (ignore_index, out of range, past the end)
 __device__ __forceinline__ int lane_label(const int64_t* __restrict__ labels, long long r, long long rows, int C,
                                           long long ignore, const float* __restrict__ class_w, float& wy) {
@@ -76,15 +58,16 @@ __global__ __launch_bounds__(256) void term_fwd_kernel(const T* __restrict__ x, 
 #pragma unroll
     for (int c = 0; c < CP; ++c) acc[c] = 0.f;
     for (int j = 4 * lane; j < d4; j += 256) {
-      const float4 xv = ld_act4(xr + j);
+      float xv[4];
+      ld_vec<4>(xr + j, xv);
 #pragma unroll
       for (int c = 0; c < CP; ++c)
         if (c < C) {
           const float4 wv = *(const float4*)(W + c * ldw + j);
-          acc[c] = fmaf(xv.x, wv.x, acc[c]);
-          acc[c] = fmaf(xv.y, wv.y, acc[c]);
-          acc[c] = fmaf(xv.z, wv.z, acc[c]);
-          acc[c] = fmaf(xv.w, wv.w, acc[c]);
+          acc[c] = fmaf(xv[0], wv.x, acc[c]);
+          acc[c] = fmaf(xv[1], wv.y, acc[c]);
+          acc[c] = fmaf(xv[2], wv.z, acc[c]);
+          acc[c] = fmaf(xv[3], wv.w, acc[c]);
         }
     }
     for (int j = d4 + lane; j < d; j += 64) {
@@ -113,8 +96,8 @@ __global__ __launch_bounds__(256) void term_fwd_kernel(const T* __restrict__ x, 
     }
     if (lane == u) my = wy * (lse - ly);
   }
-  const double num = wave_sum_f64((double)my);
-  const double den = wave_sum_f64((double)wy);
+  const double num = wave_sum((double)my);
+  const double den = wave_sum((double)wy);
   if (lane == 0) {
     lpart[2 * chunk] = num;
     lpart[2 * chunk + 1] = den;
@@ -195,8 +178,7 @@ __global__ __launch_bounds__(64) void term_bwd_kernel(const T* __restrict__ x, l
   auto load_x = [&](int u, float* v) __attribute__((always_inline)) {
     const T* __restrict__ p = x + (base + u) * ldx + col0;
     if (full) {
-      const float4 t = ld_act4(p);
-      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+      ld_vec<4>(p, v);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = col0 + k < d ? ld_act<T>(p + k) : 0.f;
@@ -285,7 +267,6 @@ __global__ __launch_bounds__(256) void term_reduce_kernel(const float* __restric
   }
 }
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 struct TcLayout {
   size_t hdr, lpart, prob, dbpart, dwpart, total;
   long long nchunk;
@@ -295,10 +276,10 @@ inline TcLayout tc_layout(long long rows, int d, int C) {
   L.nchunk = (rows + TC_ROWS - 1) / TC_ROWS;
   L.hdr = 0;
   L.lpart = 16;
-  L.prob = L.lpart + up16((size_t)L.nchunk * 2 * sizeof(double));
-  L.dbpart = L.prob + up16((size_t)rows * C * sizeof(float));
-  L.dwpart = L.dbpart + up16((size_t)L.nchunk * TC_MAXC * sizeof(float));
-  L.total = L.dwpart + up16((size_t)L.nchunk * C * d * sizeof(float));
+  L.prob = L.lpart + cg_rup((size_t)L.nchunk * 2 * sizeof(double), 16);
+  L.dbpart = L.prob + cg_rup((size_t)rows * C * sizeof(float), 16);
+  L.dwpart = L.dbpart + cg_rup((size_t)L.nchunk * TC_MAXC * sizeof(float), 16);
+  L.total = L.dwpart + cg_rup((size_t)L.nchunk * C * d * sizeof(float), 16);
   return L;
 }
 

@@ -257,6 +257,25 @@ class AttnStatsDesc(C.Structure):
                 ("workspace", vp), ("ws_bytes", sz)]
 
 
+NGRAM_INDEX_MAX_N = 32  # CG_NGRAM_INDEX_MAX_N: the longest window of cg_ngram_index_build
+NGRAM_INDEX_MAX_SYM = 2 ** 32 - 2  # CG_NGRAM_INDEX_MAX_SYM: 0xFFFFFFFF is the table's empty slot
+NGRAM_MAX_QUERY = 16384  # CG_NGRAM_MAX_QUERY: the longest query of cg_ngram_coverage
+NGRAM_INDEX_EMPTY = 0xFFFFFFFF
+
+
+class NgramIndexDesc(C.Structure):
+    """cg_ngram_index_desc: n_unique and n_dropped are optional (None = not wanted)"""
+    _fields_ = [("sym", vp), ("n_sym", i64), ("offsets", vp), ("n_seq", i32), ("seq_lo", i32), ("seq_hi", i32),
+                ("n", i32), ("table", vp), ("capacity", i64), ("n_unique", vp), ("n_dropped", vp)]
+
+
+class NgramCoverageDesc(C.Structure):
+    """cg_ngram_coverage_desc: hit, n_hit and covered are optional (None = not wanted)"""
+    _fields_ = [("sym", vp), ("n_sym", i64), ("n", i32), ("table", vp), ("capacity", i64),
+                ("qsym", vp), ("n_qsym", i64), ("qoffsets", vp), ("n_q", i32), ("max_qlen", i32),
+                ("hit", vp), ("n_hit", vp), ("covered", vp)]
+
+
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {
     "cg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -365,6 +384,8 @@ SIGNATURES = {
     "cg_attn_stats_workspace": (sz, [i32, i32, i32]),
     "cg_attn_stats": (i32, [C.POINTER(AttnStatsDesc), vp]),
     "cg_model_attn_stats": (i32, [C.POINTER(Model), i32, C.POINTER(AttnStatsDesc), vp]),
+    "cg_ngram_index_build": (i32, [C.POINTER(NgramIndexDesc), vp]),
+    "cg_ngram_coverage": (i32, [C.POINTER(NgramCoverageDesc), vp]),
     "cg_shape_targets": (i32, [vp, i32, i32, C.POINTER(i32), i32, vp, i64, vp, vp]),
     "cg_gram_workspace": (sz, [i64, i32, i32, i32]),
     "cg_gram_accum": (i32, [i32, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, vp, i64, vp, sz, vp]),

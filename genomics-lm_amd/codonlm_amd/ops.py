@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1326,3 +1327,119 @@ def gram_accum(h, y, grp, G, gram=None, *, m=None, accumulate=False, workspace=N
                                 1 if accumulate else 0, gram.data_ptr(), max(int(gram.stride(1)), P), ws.data_ptr(),
                                 ws.numel() * ws.element_size(), L.stream_ptr(dev)), "cg_gram_accum")
     return gram
+
+
+def _seq_set(sym, offsets, what):
+    """(device uint8 flat symbols, device int64 offsets, host int64 offsets) of a sequence set; offsets may be
+    a host array or a device tensor (read back once)."""
+    L.require_device(sym, what)
+    if sym.dtype != torch.uint8 or sym.dim() != 1 or not sym.is_contiguous():
+        raise ValueError(f"{what}: symbols are a flat contiguous uint8 tensor")
+    if sym.data_ptr() % 4:
+        raise ValueError(f"{what}: the symbol buffer must be 4-byte aligned")
+    host = (offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)).astype(np.int64)
+    if host.ndim != 1 or host.size < 1 or (np.diff(host) < 0).any() or host[0] < 0 or host[-1] > sym.numel():
+        raise ValueError(f"{what}: offsets are non-decreasing, start at or after 0 and end within the symbols")
+    if sym.numel() > L.NGRAM_INDEX_MAX_SYM:
+        raise ValueError(f"{what}: more than 2^32 - 2 symbols (CG_EUNSUPPORTED)")
+    dev_off = offsets if isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.dtype == torch.int64 \
+        else torch.from_numpy(host).to(sym.device)
+    return sym, dev_off.contiguous(), host
+
+
+def ngram_window_count(offsets, n: int, lo: int = 0, hi=None) -> int:
+    """The number of windows of n symbols of the sequences [lo, hi) of host ``offsets``."""
+    lens = np.diff(np.asarray(offsets, dtype=np.int64))[lo:hi]
+    return int(np.maximum(lens - int(n) + 1, 0).sum())
+
+
+class NgramIndex:
+    """An exact window-membership index over the sequence set (``sym`` device uint8, ``offsets``
+    int64 [n_seq + 1]) for windows of ``n`` symbols: the open-addressing ``table`` of
+    cg_ngram_index_build (uint32 [capacity], filled with empty slots here), ``n_unique`` (device int64 [1],
+    the distinct windows inserted so far) and ``n_dropped`` (stays 0).  The default capacity is the
+    smallest power of two >= 2 x the windows of the whole set; ``capacity=`` overrides it (a power of two
+    above the window count)."""
+    __slots__ = ("sym", "offsets", "host_offsets", "n", "table", "capacity", "n_unique", "n_dropped")
+
+    def __init__(self, sym, offsets, n: int, capacity=None):
+        n = int(n)
+        if not 1 <= n <= L.NGRAM_INDEX_MAX_N:
+            raise ValueError(f"ngram index: window of {n} symbols outside 1..{L.NGRAM_INDEX_MAX_N}")
+        self.sym, self.offsets, self.host_offsets = _seq_set(sym, offsets, "ngram index")
+        self.n = n
+        windows = ngram_window_count(self.host_offsets, n)
+        if capacity is None:
+            capacity = 2
+            while capacity < 2 * windows:
+                capacity *= 2
+        capacity = int(capacity)
+        if capacity < 2 or capacity & (capacity - 1) or capacity <= windows or capacity > 2 ** 32:
+            raise ValueError(f"ngram index: capacity {capacity} must be a power of two in 2..2^32 above the "
+                             f"{windows} windows of the set")
+        dev = sym.device
+        self.capacity = capacity
+        # 0xFFFFFFFF = the empty slot
+        self.table = torch.full((capacity,), -1, dtype=torch.int32, device=dev)
+        self.n_unique = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.n_dropped = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    @property
+    def n_seq(self) -> int:
+        return int(self.host_offsets.size - 1)
+
+
+def ngram_index_build(index: NgramIndex, seq_lo: int = 0, seq_hi=None) -> NgramIndex:
+    """cg_ngram_index_build: insert every window of the sequences [seq_lo, seq_hi) (default: all) of the
+    index's own set.  Launches over disjoint ranges add up to the build of their union; inserting a
+    range twice leaves the set and ``n_unique`` unchanged."""
+    seq_hi = index.n_seq if seq_hi is None else int(seq_hi)
+    seq_lo = int(seq_lo)
+    if not 0 <= seq_lo <= seq_hi <= index.n_seq:
+        raise ValueError(f"ngram_index_build: sequences [{seq_lo}, {seq_hi}) outside 0..{index.n_seq}")
+    d = L.NgramIndexDesc()
+    d.sym, d.n_sym = index.sym.data_ptr(), index.sym.numel()
+    d.offsets, d.n_seq, d.seq_lo, d.seq_hi = index.offsets.data_ptr(), index.n_seq, seq_lo, seq_hi
+    d.n, d.table, d.capacity = index.n, index.table.data_ptr(), index.capacity
+    d.n_unique, d.n_dropped = index.n_unique.data_ptr(), index.n_dropped.data_ptr()
+    L.check(L.lib.cg_ngram_index_build(C.byref(d), L.stream_ptr(index.sym.device)), "cg_ngram_index_build")
+    return index
+
+
+class NgramCoverage:
+    """Device tensors of one ngram_coverage call; an output that was not asked for is None."""
+    __slots__ = ("hit", "n_hit", "covered")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
+COVERAGE_OUTPUTS = ("hit", "n_hit", "covered")
+
+
+def ngram_coverage(index: NgramIndex, qsym, qoffsets, want=("n_hit", "covered")) -> NgramCoverage:
+    """cg_ngram_coverage of the query set (``qsym`` device uint8, ``qoffsets`` int64 [n_q + 1]) against a
+    built index: ``hit`` uint8 like qsym (1 at the starts of windows the index holds), ``n_hit`` int32
+    [n_q], ``covered`` int32 [n_q] (positions inside at least one hit window).  A query longer than
+    16384 symbols raises ValueError (CG_EUNSUPPORTED)."""
+    unknown = set(want) - set(COVERAGE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"ngram_coverage: unknown outputs {sorted(unknown)}")
+    qsym, qoff, host = _seq_set(qsym, qoffsets, "ngram_coverage")
+    n_q = int(host.size - 1)
+    dev = qsym.device
+    d = L.NgramCoverageDesc()
+    d.sym, d.n_sym, d.n = index.sym.data_ptr(), index.sym.numel(), index.n
+    d.table, d.capacity = index.table.data_ptr(), index.capacity
+    d.qsym, d.n_qsym, d.qoffsets, d.n_q = qsym.data_ptr(), qsym.numel(), qoff.data_ptr(), n_q
+    d.max_qlen = int(np.diff(host).max()) if n_q else 0
+    res = NgramCoverage()
+    for name, t in (("hit", lambda: torch.zeros(qsym.numel(), dtype=torch.uint8, device=dev)),
+                    ("n_hit", lambda: torch.empty(n_q, dtype=torch.int32, device=dev)),
+                    ("covered", lambda: torch.empty(n_q, dtype=torch.int32, device=dev))):
+        if name in want:
+            setattr(res, name, t())
+            setattr(d, name, getattr(res, name).data_ptr())
+    L.check(L.lib.cg_ngram_coverage(C.byref(d), L.stream_ptr(dev)), "cg_ngram_coverage")
+    return res

@@ -103,6 +103,27 @@ def token_logprobs(model, ids, *, batch_size: int = 32) -> np.ndarray:
     return logp.cpu().numpy()
 
 
+@torch.no_grad()
+def token_logprobs_batch(model, seqs: Sequence[Sequence[int]], *, batch_size: int = 32) -> List[np.ndarray]:
+    """``token_logprobs`` of many sequences (each at most block_size + 1 tokens) in length-bucketed
+    batches, in input order: per sequence the fp32 log p(ids[t] | ids[:t]) for t = 1..len-1, with 0
+    where the target is PAD (0), as F.cross_entropy(ignore_index=0) leaves it.  One read-back."""
+    if not len(seqs):
+        return []
+    eng = model.engine
+    parts = []
+    for b, x, y in _batches(model, seqs, batch_size, int(model.block_size) + 1):
+        parts.append((b, x.shape[1], eng.score(x, y, ignore_index=PAD_ID, want=("logp",)).logp))
+    logps = torch.cat([lp.reshape(-1) for _, _, lp in parts]).cpu().numpy()
+    out: List[np.ndarray] = [None] * len(seqs)
+    row = 0
+    for b, T, _ in parts:
+        for j, i in enumerate(b):
+            out[i] = logps[row + j * T: row + j * T + len(seqs[i]) - 1].copy()
+        row += len(b) * T
+    return out
+
+
 def _upload(seqs, dev):
     """One upload of all sequences: (flat int32 tokens, starts int64, lens int64) on the device."""
     lens = np.array([len(s) for s in seqs], dtype=np.int64)
@@ -269,5 +290,6 @@ def evaluate(model, batches: Iterable, *, label_smoothing: float = 0.0, offset_t
     return mean_nll, math.exp(min(20.0, mean_nll)), mean_obj, total, metrics
 
 
-__all__ = ["CODONS", "DEFAULT_VOCAB", "dna_to_ids", "codon_ids", "sliding_windows", "token_logprobs", "score_batch",
+__all__ = ["CODONS", "DEFAULT_VOCAB", "dna_to_ids", "codon_ids", "sliding_windows", "token_logprobs", "token_logprobs_batch",
+           "score_batch",
            "score_variants", "mutation_map", "mutation_maps", "evaluate", "batch_order"]

@@ -1857,7 +1857,7 @@ extern "C" size_t cg_struct_bytes(const char* name) {
   CG_SZ(cg_param_entry) CG_SZ(cg_model) CG_SZ(cg_model_opts) CG_SZ(cg_sample_params) CG_SZ(cg_gen_state)
   CG_SZ(cg_score_desc) CG_SZ(cg_sample_plan) CG_SZ(cg_offset_prior) CG_SZ(cg_attr_desc)
   CG_SZ(cg_kmeans_desc) CG_SZ(cg_term_ce_desc) CG_SZ(cg_ngram_nll_desc) CG_SZ(cg_diag_desc)
-  CG_SZ(cg_attn_stats_desc)
+  CG_SZ(cg_attn_stats_desc) CG_SZ(cg_ngram_index_desc) CG_SZ(cg_ngram_coverage_desc)
 #undef CG_SZ
   return 0;
 }

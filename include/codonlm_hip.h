@@ -1171,6 +1171,75 @@ int cg_gram_accum(int dtype, const void* h, long long ldh, int d, const float* y
                   const int32_t* grp, long long rows, int G, int accumulate, double* gram, long long ldg,
                   void* workspace, size_t ws_bytes, void* stream);
 
+/* Memorization audit (ABI 0.6 addition): an exact window-membership index over byte symbols.  It replaces
+ * the Python set of n-gram tuples of the reference's scripts/eval_generation_prefix.py
+ * (_build_train_ngram_set :164-206, capped at 10M tokens "to prevent RAM bloat", and
+ * _training_match_coverage :472-482) and the window index of src/codonlm/leakage_audit.py
+ * (matching_substring_coverage, _coverage_from_index, _matched_query_windows), which runs over nucleotide
+ * windows of 30 and protein windows of 10.
+ * Symbols are uint8: token ids below 256, or the ASCII bytes of a nucleotide / protein string.  A sequence
+ * set is a flat device uint8 buffer (4-byte aligned) of n_sym symbols plus device int64 offsets[n_seq + 1],
+ * non-decreasing, offsets[n_seq] <= n_sym <= CG_NGRAM_INDEX_MAX_SYM = 2^32 - 2; sequence s is
+ * [offsets[s], offsets[s+1]).  Packed rows [R][T] are the case offsets[r] = r * T.  A window is n
+ * consecutive symbols of one sequence, 1 <= n <= CG_NGRAM_INDEX_MAX_N = 32; it never crosses a sequence
+ * boundary.  Offsets outside [0, n_sym] are clamped, so no call reads past a buffer it was given.
+ *
+ * cg_ngram_index_build inserts every window of the sequences [seq_lo, seq_hi) into table, an
+ * open-addressing table uint32 [capacity]: capacity a power of two (2 .. 2^32), strictly greater than the
+ * number of windows ever inserted; empty = 0xFFFFFFFF, which the caller fills the table with before the
+ * first build.  A slot holds the flat start position of one occurrence of its window.  Insertion: hash the
+ * n symbols (the hash is internal, a function of the symbols and n only), probe linearly with wrap-around;
+ * an empty slot is claimed with a 32-bit agent-scope compare-and-swap (the slot is read first, so a heavily
+ * duplicated window -- a pad run, low-complexity sequence -- does not hammer one address with atomics); at
+ * an occupied slot the n symbols at the stored position are compared with the window's own: equal = a
+ * duplicate, stop; different = the next slot.  Stored positions never change once written, which is all
+ * the synchronisation there is.  n_unique (optional, device int64 [1], 8-byte aligned) += the number of
+ * claims, reduced per workgroup into one integer atomic; several launches over disjoint sequence ranges of
+ * the same sym buffer give the same set and the same n_unique as one launch.  n_dropped (optional, as
+ * n_unique) += the windows that found no slot in `capacity` probes: 0 unless the caller broke the capacity
+ * rule.  WHICH duplicate's position a slot holds, and in WHICH slot a window lies, is not defined (it
+ * depends on the order the hardware ran the threads in); n_unique, n_dropped and every output of
+ * cg_ngram_coverage are defined, exact integers, the same in every run.
+ * seq_lo == seq_hi or n_sym < n: CG_OK, nothing touched.  CG_EINVAL: n < 1, a negative size, a sequence
+ * range outside [0, n_seq], NULL or misaligned sym / offsets / table, a capacity that is no power of two in
+ * 2 .. 2^32.  CG_EUNSUPPORTED: n > CG_NGRAM_INDEX_MAX_N, n_sym > CG_NGRAM_INDEX_MAX_SYM. */
+#define CG_NGRAM_INDEX_MAX_N 32
+#define CG_NGRAM_INDEX_MAX_SYM 4294967294ll
+#define CG_NGRAM_MAX_QUERY 16384
+typedef struct {
+  const uint8_t* sym; long long n_sym;
+  const int64_t* offsets; int n_seq;
+  int seq_lo, seq_hi;
+  int n;
+  uint32_t* table; long long capacity;
+  long long* n_unique;
+  long long* n_dropped;
+} cg_ngram_index_desc;
+int cg_ngram_index_build(const cg_ngram_index_desc* d, void* stream);
+/* cg_ngram_coverage: the query set (qsym [n_qsym], qoffsets [n_q + 1], as above) against a built table
+ * and the sym it was built over.  For query q of length len, every start s with s + n <= len is a HIT
+ * iff its window is in the table (probe until an equal window = hit, or an empty slot = miss).  Outputs,
+ * each optional:
+ *   hit      uint8, one per query symbol (the layout of qsym): 1 at hit starts, 0 elsewhere in the query;
+ *            bytes of qsym that belong to no query are not written;
+ *   n_hit    int32 [n_q]: the number of hit starts;
+ *   covered  int32 [n_q]: the number of positions t with a hit start s, s <= t < s + n (the reference's
+ *            coverage is covered / len, a division the caller makes).
+ * A query shorter than n gives 0 / 0.  One workgroup per query: lookups into a bit mask in LDS, a barrier,
+ * then cover and reduce.  max_qlen is the longest query as the caller states it: above CG_NGRAM_MAX_QUERY =
+ * 16384 the call is CG_EUNSUPPORTED; a query longer than max_qlen is read as its first max_qlen symbols.
+ * n_q == 0: CG_OK, nothing touched.  Otherwise the errors of cg_ngram_index_build. */
+typedef struct {
+  const uint8_t* sym; long long n_sym;
+  int n;
+  const uint32_t* table; long long capacity;
+  const uint8_t* qsym; long long n_qsym;
+  const int64_t* qoffsets; int n_q;
+  int max_qlen;
+  uint8_t* hit; int32_t* n_hit; int32_t* covered;
+} cg_ngram_coverage_desc;
+int cg_ngram_coverage(const cg_ngram_coverage_desc* d, void* stream);
+
 /* Live probe of one kernel class during a real run: HIP events are recorded on the
  * launching stream around each launch of the selected kernel together with its
  * algorithmic work (FLOPs for MFMA kernels).  kind 0 disables.  cg_probe_read
@@ -1208,7 +1277,8 @@ int cg_diag_occupy(int n_cus, int usec, void* stream);
  * "cg_reduce_batch", "cg_transpose_item", "cg_transpose_batch", "cg_adamw_segment",
  * "cg_model_cfg", "cg_param_entry", "cg_model", "cg_model_opts", "cg_sample_params", "cg_gen_state",
  * "cg_score_desc", "cg_sample_plan", "cg_offset_prior", "cg_attr_desc", "cg_kmeans_desc",
- * "cg_term_ce_desc", "cg_ngram_nll_desc", "cg_diag_desc", "cg_attn_stats_desc"), 0 for
+ * "cg_term_ce_desc", "cg_ngram_nll_desc", "cg_diag_desc", "cg_attn_stats_desc", "cg_ngram_index_desc",
+ * "cg_ngram_coverage_desc"), 0 for
  * another name: lets a binding that mirrors
  * the layouts check them against the library it loaded. */
 size_t cg_struct_bytes(const char* name);
@@ -1238,7 +1308,8 @@ size_t cg_struct_bytes(const char* name);
  * cg_ngram_nll_workspace, cg_diag_rows with cg_diag_desc and cg_diag_workspace.  ABI 0.6, additions:
  * attention head analysis -- cg_attn_stats with cg_attn_stats_desc, cg_attn_stats_workspace and
  * cg_model_attn_stats.  ABI 0.6, additions: structural regression probes -- cg_shape_targets,
- * cg_gram_accum and cg_gram_workspace. */
+ * cg_gram_accum and cg_gram_workspace.  ABI 0.6, additions: memorization audit -- cg_ngram_index_build
+ * with cg_ngram_index_desc, cg_ngram_coverage with cg_ngram_coverage_desc. */
 const char* cg_version(void);
 
 #ifdef __cplusplus

@@ -43,7 +43,7 @@ PROBE_KERNELS = {PROBE_GEMM_DW_GROUPED: ("gemm_dw_kernel",), PROBE_ATTN_FWD: ("a
 # parameter kinds (enum in the header)
 (P_TOK_EMB, P_POS_EMB, P_LN1_W, P_LN1_B, P_Q_W, P_K_W, P_V_W, P_Q_B, P_K_B, P_V_B, P_PROJ_W,
  P_PROJ_B, P_LN2_W, P_LN2_B, P_FC1_W, P_FC1_B, P_FC2_W, P_FC2_B, P_GATE_W, P_UP_W, P_DOWN_W,
- P_LNF_W, P_LNF_B, P_HEAD_W, P_TERM_W, P_TERM_B, P_OFF1_W, P_OFF1_B, P_OFF2_W, P_OFF2_B) = range(30)
+ P_LNF_W, P_LNF_B, P_HEAD_W, P_TERM_W, P_TERM_B, P_OFF1_W, P_OFF1_B, P_OFF2_W, P_OFF2_B, P_NKINDS) = range(31)
 
 vp = C.c_void_p
 i32, i64, f32, u32, sz = C.c_int, C.c_longlong, C.c_float, C.c_uint32, C.c_size_t
@@ -95,7 +95,7 @@ TRANSPOSE_MAX = 64
 
 
 class TransposeItem(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("lds", i64), ("ldd", i64), ("rows", i32), ("cols", i32)]
+    _fields_ = [("src", vp), ("dst", vp), ("lds", i64), ("ldd", i64), ("rows", i32), ("cols", i32)]
 
 
 class TransposeBatch(C.Structure):
@@ -275,6 +275,22 @@ class NgramCoverageDesc(C.Structure):
                 ("qsym", vp), ("n_qsym", i64), ("qoffsets", vp), ("n_q", i32), ("max_qlen", i32),
                 ("hit", vp), ("n_hit", vp), ("covered", vp)]
 
+
+SHAPE_TARGETS = 14  # CG_SHAPE_TARGETS: the DNAshape columns cg_shape_targets writes per position
+
+# header struct name -> ctypes mirror, for every `typedef struct { ... } cg_x;` of include/codonlm_hip.h
+# (tests/test_binding_cpu.py compares sizes, field names, order and kinds with the header)
+STRUCTS = {
+    "cg_gemm_desc": GemmDesc, "cg_dw_product": DwProduct, "cg_dw_group": DwGroup, "cg_reduce_job": ReduceJob,
+    "cg_reduce_batch": ReduceBatch, "cg_transpose_item": TransposeItem, "cg_transpose_batch": TransposeBatch,
+    "cg_adamw_segment": AdamwSegment, "cg_model_opts": ModelOpts, "cg_model_cfg": ModelCfg,
+    "cg_param_entry": ParamEntry, "cg_model": Model, "cg_offset_prior": OffsetPrior,
+    "cg_sample_params": SampleParams, "cg_gen_state": GenState, "cg_sample_plan": SamplePlan,
+    "cg_score_desc": ScoreDesc, "cg_attr_desc": AttrDesc, "cg_kmeans_desc": KMeansDesc,
+    "cg_term_ce_desc": TermCeDesc, "cg_ngram_nll_desc": NgramNllDesc, "cg_diag_desc": DiagDesc,
+    "cg_attn_stats_desc": AttnStatsDesc, "cg_ngram_index_desc": NgramIndexDesc,
+    "cg_ngram_coverage_desc": NgramCoverageDesc,
+}
 
 # name -> (restype, argtypes) for every symbol include/codonlm_hip.h declares
 SIGNATURES = {

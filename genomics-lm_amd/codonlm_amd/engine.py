@@ -222,7 +222,7 @@ class Engine:
         self.score_logits = buf[:B * T * V].view(B, T, V)
         self.forward(idx, None, training=False, window=window, logits=self.score_logits)
         wsb = getattr(self, "_score_ws", None)
-        if wsb is None or wsb.numel() * 8 < int(L.lib.cg_score_workspace(B * T)) or wsb.device != buf.device:
+        if wsb is None or ops._nbytes(wsb) < int(L.lib.cg_score_workspace(B * T)) or wsb.device != buf.device:
             wsb = self._score_ws = ops.score_workspace(B * T, buf.device)
         return ops.score_rows(self.score_logits.view(B * T, V), targets, T=T, workspace=wsb, **kw)
 
@@ -377,9 +377,7 @@ class Engine:
             raise ValueError("input_grad: no forward has run")
         if mode not in ops.ATTR_MODES:
             raise ValueError(f"input_grad: mode is one of {sorted(ops.ATTR_MODES)}")
-        unknown = set(want) - set(ops.ATTR_OUTPUTS)
-        if unknown:
-            raise ValueError(f"input_grad: unknown outputs {sorted(unknown)}")
+        ops._check_want("input_grad", want, ops.ATTR_OUTPUTS)
         dev = self.flat.device
         a = L.AttrDesc()
         a.mode = ops.ATTR_MODES[mode]
@@ -391,20 +389,11 @@ class Engine:
                 raise ValueError("input_grad: a seeded call replaced the forward's loss gradient; run the forward again")
         else:
             for name, t, dt in (("y", y, torch.int64), ("w", w, torch.float32)):
-                if t is None:
-                    continue
-                L.require_device(t, "input_grad")
-                if t.numel() != B * T:
-                    raise ValueError(f"input_grad: {name} has one entry per position of the forward, ({B}, {T})")
-                t = t.reshape(-1).to(dtype=dt).contiguous()
-                keep.append(t)
-                setattr(a, name, t.data_ptr())
+                if t is not None:  # one entry per position of the forward
+                    keep.append(ops._per_row(t, "input_grad", name, dt, B * T))
+                    setattr(a, name, keep[-1].data_ptr())
         res = ops.AttrResult()
-        for name in ops.ATTR_OUTPUTS:
-            if name in want:
-                t = torch.empty(B, T, dtype=torch.float32, device=dev)
-                setattr(res, name, t)
-                setattr(a, name, t.data_ptr())
+        ops._alloc_outputs(a, res, want, dev, [(name, (B, T), torch.float32) for name in ops.ATTR_OUTPUTS])
         if dx0:
             res.dx0 = torch.empty(B, T, d, dtype=torch.float32, device=dev)
             a.dx0, a.ld_dx0 = res.dx0.data_ptr(), d

@@ -27,6 +27,92 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+class _Result:
+    """Base of the result classes: every slot None unless given, in slot order or by keyword."""
+    __slots__ = ()
+
+    def __init__(self, *args, **given):
+        for k in self.__slots__:
+            setattr(self, k, None)
+        for k, v in zip(self.__slots__, args):
+            setattr(self, k, v)
+        for k, v in given.items():  # a name that is no slot is an AttributeError
+            setattr(self, k, v)
+
+
+def _check_want(what, want, allowed):
+    unknown = set(want) - set(allowed)
+    if unknown:
+        raise ValueError(f"{what}: unknown outputs {sorted(unknown)}")
+
+
+def _alloc_outputs(desc, res, want, dev, table, zero=()):
+    """For each (name, shape, dtype) of ``table`` named in ``want``: allocate the tensor (torch.empty;
+    torch.zeros for the names in ``zero``), set it on ``res`` and its pointer on ``desc`` (None: the
+    entry point takes the pointers as arguments)."""
+    for name, shape, dt in table:
+        if name in want:
+            t = (torch.zeros if name in zero else torch.empty)(shape, dtype=dt, device=dev)
+            setattr(res, name, t)
+            if desc is not None:
+                setattr(desc, name, t.data_ptr())
+
+
+def _nbytes(t) -> int:
+    return t.numel() * t.element_size()
+
+
+def _set_ws(desc, ws):
+    desc.workspace, desc.ws_bytes = ws.data_ptr(), _nbytes(ws)
+
+
+def _alloc_ws(need, dev, kind):
+    """A workspace of at least ``need`` bytes: "f64" = fp64 of need // 8 + 1 (8-byte aligned, the
+    accumulating ops), "u8" = uint8 of max(need, 16), "u8_256" = uint8 of max(need, 256)."""
+    need = int(need)
+    if kind == "f64":
+        return torch.empty(need // 8 + 1, dtype=torch.float64, device=dev)
+    return torch.empty(max(need, {"u8": 16, "u8_256": 256}[kind]), dtype=torch.uint8, device=dev)
+
+
+def _pick_ws(ws, dev, kind, grow, need, *args):
+    """The workspace of a launch.  ``grow`` False: the caller's ``ws`` as given (the library answers
+    a short one with CG_EINVAL), a fresh one only without it.  ``grow`` True: the caller's if it
+    holds the bytes, else a fresh one.  ``need(*args)`` is the library's sizing entry point, asked
+    only when it decides something; ``args`` are Python ints (ctypes converts them, nothing else)."""
+    if ws is not None and not grow:
+        return ws
+    n = int(need(*args))
+    return ws if ws is not None and _nbytes(ws) >= n else _alloc_ws(n, dev, kind)
+
+
+def _row_matrix(t, what, dtypes=(torch.float32,), *, loose=False, width=None):
+    """Check a [rows][ld] matrix with contiguous rows and return its row stride.  Two conventions:
+    strict (score / attr / diag): every matrix with rows needs unit column stride, and one without
+    rows has the stride ``width`` (default: its own width);  ``loose`` (kmeans / term_ce): a
+    one-column matrix may have any column stride, and a single row's stride is at least its width."""
+    if t.dim() != 2 or t.dtype not in dtypes or ((t.shape[1] > 1 if loose else t.shape[0]) and t.stride(1) != 1):
+        raise ValueError(f"{what} is a {' / '.join(str(d) for d in dtypes)} [rows][ld] matrix with contiguous rows")
+    if loose:
+        return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+    return t.stride(0) if t.shape[0] else (t.shape[1] if width is None else int(width))
+
+
+def _per_row(t, what, name, dtype, rows):
+    """One value per row: ``t`` on the device, flattened, as contiguous ``dtype`` [rows]."""
+    L.require_device(t, what)
+    t = t.reshape(-1).to(dtype).contiguous()
+    if t.numel() != rows:
+        raise ValueError(f"{what}: one {name} per row ({rows} rows)")
+    return t
+
+
+def _dev_tensor(t, dtype, numel, what):
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{what} is a contiguous device {dtype} of {numel} elements")
+    return t.data_ptr()
+
+
 def gemm(a, b, *, a_kcontig=True, b_kcontig=True, M=None, N=None, K=None, out=None, out_dtype=None,
          bias=None, resid=None, epilogue=0, aux=None, aux_out=None, alpha=1.0, drop_seed=0, drop_p=0.0,
          split_k=1, colsum_out=None, n_valid=0, rope=None, tile=0, max_wg=0):
@@ -71,8 +157,9 @@ def gemm(a, b, *, a_kcontig=True, b_kcontig=True, M=None, N=None, K=None, out=No
     aux_t = aux if aux is not None else aux_out
     d.ld_aux = aux_t.stride(0) if aux_t is not None else 0
     d.drop_seed, d.drop_p = int(drop_seed) & 0xFFFFFFFF, float(drop_p)
-    d.split_k, d.workspace = int(split_k), _p(ws)
-    d.ws_bytes = 0 if ws is None else ws.numel() * ws.element_size()
+    d.split_k = int(split_k)
+    if ws is not None:
+        _set_ws(d, ws)
     d.n_valid = int(n_valid)
     d.tile, d.max_wg = int(tile), int(max_wg)
     if rope is not None:
@@ -87,12 +174,17 @@ def gemm(a, b, *, a_kcontig=True, b_kcontig=True, M=None, N=None, K=None, out=No
     return out
 
 
-def layernorm_fwd(x, weight, bias, out_dtype=torch.float32, eps=1e-5):
-    L.require_device(x, "layernorm_fwd")
+def _ln_fwd_outputs(x, out_dtype):
+    """(rows, cols, y, mean, rstd) of a LayerNorm forward over x [rows][cols]."""
     rows, cols = x.shape
     y = torch.empty(rows, cols, dtype=out_dtype, device=x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty_like(mean)
+    return rows, cols, y, mean, torch.empty_like(mean)
+
+
+def layernorm_fwd(x, weight, bias, out_dtype=torch.float32, eps=1e-5):
+    L.require_device(x, "layernorm_fwd")
+    rows, cols, y, mean, rstd = _ln_fwd_outputs(x, out_dtype)
     L.check(L.lib.cg_layernorm_fwd(_dt(y), x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(),
                                    y.data_ptr(), y.stride(0), mean.data_ptr(), rstd.data_ptr(), rows, cols, eps,
                                    L.stream_ptr(x.device)), "cg_layernorm_fwd")
@@ -103,10 +195,7 @@ def layernorm_fwd_mask(x, weight, bias, B, T, H, drop_seed, drop_p, out_dtype=to
     """cg_layernorm_fwd_mask: layernorm_fwd and the attention-dropout keep words (attn_drop_mask) in one
     launch -> (y, mean, rstd, mask)."""
     L.require_device(x, "layernorm_fwd_mask")
-    rows, cols = x.shape
-    y = torch.empty(rows, cols, dtype=out_dtype, device=x.device)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty_like(mean)
+    rows, cols, y, mean, rstd = _ln_fwd_outputs(x, out_dtype)
     n = int(L.lib.cg_attn_drop_mask_bytes(B, T, H))
     mask = torch.zeros(max(n, 4) // 4, dtype=torch.int32, device=x.device)
     L.check(L.lib.cg_layernorm_fwd_mask(_dt(y), x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(),
@@ -154,7 +243,7 @@ def layernorm_bwd_partials(dy, x, mean, rstd, weight, g_in=None, branch_dtype=No
                                             mean.data_ptr(), rstd.data_ptr(), weight.data_ptr(), _p(g_in),
                                             g_out.data_ptr(), _dt(branch) if branch is not None else L.CG_F32,
                                             _p(branch), drop_seed, drop_p, part.data_ptr(),
-                                            part.numel() * 4, int(nw == 3), rows, cols,
+                                            _nbytes(part), int(nw == 3), rows, cols,
                                             L.stream_ptr(x.device)), "cg_layernorm_bwd_partials")
     return g_out, part, branch
 
@@ -256,7 +345,7 @@ def attn_bwd(qkv, segstart, y, dy, lse, B, T, H, KV, hd, window=0, drop_seed=0, 
             dy.stride(0), lse.data_ptr(), dqkv.data_ptr(), dqkv.stride(0), B, T, H, KV, hd, int(window or 0),
             int(drop_seed) & 0xFFFFFFFF, float(drop_p), _p(drop_mask), _p(bias_part),
             0 if bias_part is None else bias_part.stride(0)]
-    tail = [ws.data_ptr(), ws.numel() * 4, L.stream_ptr(qkv.device)]
+    tail = [ws.data_ptr(), _nbytes(ws), L.stream_ptr(qkv.device)]
     if algo is not None:
         rp = [None, None] if rope is None else [rope[0].data_ptr(), rope[1].data_ptr()]
         L.check(L.lib.cg_attn_bwd_algo(ATTN_BWD_ALGO[algo], *args, *rp, *tail), "cg_attn_bwd_algo")
@@ -282,7 +371,7 @@ def cross_entropy(logits, targets, eps=0.0, weight=None, ignore_index=0, grad_dt
     L.check(L.lib.cg_cross_entropy(logits.data_ptr(), logits.stride(0), targets.contiguous().data_ptr(), rows, V,
                                    float(eps), _p(weight), int(ignore_index), float(grad_scale),
                                    L.CG_BF16X2 if split else _dt(dl), dl.data_ptr(), ldd,
-                                   loss.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr(logits.device)),
+                                   loss.data_ptr(), ws.data_ptr(), _nbytes(ws), L.stream_ptr(logits.device)),
             "cg_cross_entropy")
     return loss, dl
 
@@ -384,19 +473,25 @@ def embed_fwd(idx, tok_emb, pos_emb=None, drop_seed=0, drop_p=0.0, out=None):
     return out
 
 
+def _decode_cache_check(what, q, cache, Tmax):
+    """(B, Tmax) of a decode step's q [B][>= H hd] and KV cache [B][Tmax][ldc] (Tmax None = the cache's)."""
+    if q.dtype != cache.dtype or cache.dim() != 3 or cache.stride(2) != 1 or q.stride(1) != 1:
+        raise ValueError(f"{what}: q and cache share a dtype; cache is [B][Tmax][ldc]")
+    B = q.shape[0]
+    if Tmax is None:
+        Tmax = cache.shape[1]
+    if cache.shape[0] != B or cache.stride(0) != Tmax * cache.stride(1):
+        raise ValueError(f"{what}: cache rows of one sequence must be Tmax consecutive rows")
+    return B, Tmax
+
+
 def attn_decode(q, cache, pos, H, KV, hd, segstate=None, window=0, Tmax=None):
     """One-token attention over a KV cache: q [B][>= H hd], cache [B][Tmax][ldc] (K head kvh at
     column kvh hd, V at KV hd + kvh hd); the query of position `pos` sees keys lo..pos, lo =
     segstate[b] (int32 [B], None = 0) raised to pos - window + 1 with a window -> y [B][H hd]."""
     L.require_device(q, "attn_decode")
     L.require_device(cache, "attn_decode")
-    if q.dtype != cache.dtype or cache.dim() != 3 or cache.stride(2) != 1 or q.stride(1) != 1:
-        raise ValueError("attn_decode: q and cache share a dtype; cache is [B][Tmax][ldc]")
-    B = q.shape[0]
-    if Tmax is None:
-        Tmax = cache.shape[1]
-    if cache.shape[0] != B or cache.stride(0) != Tmax * cache.stride(1):
-        raise ValueError("attn_decode: cache rows of one sequence must be Tmax consecutive rows")
+    B, Tmax = _decode_cache_check("attn_decode", q, cache, Tmax)
     y = torch.empty(B, H * hd, dtype=q.dtype, device=q.device)
     L.check(L.lib.cg_attn_decode(_dt(q), q.data_ptr(), q.stride(0), cache.data_ptr(), cache.stride(1), int(Tmax),
                                  int(pos), _p(segstate), int(window or 0), B, H, KV, hd, y.data_ptr(), y.stride(0),
@@ -411,13 +506,7 @@ def attn_decode_ragged(q, cache, pos, H, KV, hd, segstate=None, window=0, Tmax=N
     L.require_device(q, "attn_decode_ragged")
     L.require_device(cache, "attn_decode_ragged")
     L.require_device(pos, "attn_decode_ragged")
-    if q.dtype != cache.dtype or cache.dim() != 3 or cache.stride(2) != 1 or q.stride(1) != 1:
-        raise ValueError("attn_decode_ragged: q and cache share a dtype; cache is [B][Tmax][ldc]")
-    B = q.shape[0]
-    if Tmax is None:
-        Tmax = cache.shape[1]
-    if cache.shape[0] != B or cache.stride(0) != Tmax * cache.stride(1):
-        raise ValueError("attn_decode_ragged: cache rows of one sequence must be Tmax consecutive rows")
+    B, Tmax = _decode_cache_check("attn_decode_ragged", q, cache, Tmax)
     if pos.dtype != torch.int32 or pos.numel() != B or not pos.is_contiguous():
         raise ValueError("attn_decode_ragged: pos is a contiguous int32 [B]")
     y = out if out is not None else torch.zeros(B, H * hd, dtype=q.dtype, device=q.device)
@@ -427,15 +516,21 @@ def attn_decode_ragged(q, cache, pos, H, KV, hd, segstate=None, window=0, Tmax=N
     return y
 
 
-def sample_step(params, logits, state, next_tok, out_ids, n_active=None, term_logits=None):
-    """cg_sample_step in place: ``params`` a _lib.SampleParams, logits fp32 [B][V], state int32 [B][8]
-    (cg_gen_state rows), next_tok int64 [B], out_ids int64 [B][cap], n_active int32 [1]."""
+def _sample_args_check(what, logits, state, next_tok, out_ids):
+    """B of a sampling step's device tensors: logits fp32 [B][V], state int32 [B][8], int64 ids."""
     for t in (logits, state, next_tok, out_ids):
-        L.require_device(t, "sample_step")
+        L.require_device(t, what)
     B = logits.shape[0]
     if (logits.dtype != torch.float32 or state.dtype != torch.int32 or tuple(state.shape) != (B, 8)
             or not state.is_contiguous() or next_tok.dtype != torch.int64 or out_ids.dtype != torch.int64):
-        raise ValueError("sample_step: logits fp32 [B][V], state int32 [B][8], next_tok / out_ids int64")
+        raise ValueError(f"{what}: logits fp32 [B][V], state int32 [B][8], next_tok / out_ids int64")
+    return B
+
+
+def sample_step(params, logits, state, next_tok, out_ids, n_active=None, term_logits=None):
+    """cg_sample_step in place: ``params`` a _lib.SampleParams, logits fp32 [B][V], state int32 [B][8]
+    (cg_gen_state rows), next_tok int64 [B], out_ids int64 [B][cap], n_active int32 [1]."""
+    B = _sample_args_check("sample_step", logits, state, next_tok, out_ids)
     L.check(L.lib.cg_sample_step(C.byref(params), logits.data_ptr(), logits.stride(0), _p(term_logits),
                                  term_logits.stride(0) if term_logits is not None else 0, state.data_ptr(),
                                  next_tok.data_ptr(), out_ids.data_ptr(), out_ids.stride(0), _p(n_active), B,
@@ -446,12 +541,7 @@ def sample_step_plan(params, plan, logits, state, next_tok, out_ids, n_active=No
     """cg_sample_step_plan in place: sample_step's arguments plus ``plan``, a _lib.SamplePlan whose
     pointers the caller keeps alive (sets uint8 [n_sets][ld_sets], plan int32 [B][ld_plan], plan_len
     int32 [B], logp fp64 [B][2], tok_logp fp32 [B][ld_tok_logp])."""
-    for t in (logits, state, next_tok, out_ids):
-        L.require_device(t, "sample_step_plan")
-    B = logits.shape[0]
-    if (logits.dtype != torch.float32 or state.dtype != torch.int32 or tuple(state.shape) != (B, 8)
-            or not state.is_contiguous() or next_tok.dtype != torch.int64 or out_ids.dtype != torch.int64):
-        raise ValueError("sample_step_plan: logits fp32 [B][V], state int32 [B][8], next_tok / out_ids int64")
+    B = _sample_args_check("sample_step_plan", logits, state, next_tok, out_ids)
     L.check(L.lib.cg_sample_step_plan(C.byref(params), C.byref(plan) if plan is not None else None,
                                       logits.data_ptr(), logits.stride(0), _p(term_logits),
                                       term_logits.stride(0) if term_logits is not None else 0, state.data_ptr(),
@@ -474,13 +564,9 @@ def gather_rows(src, sel, T):
     return out
 
 
-class ScoreResult:
+class ScoreResult(_Result):
     """Device tensors of one score_rows call; an output that was not asked for is None."""
     __slots__ = ("lse", "logp", "entropy", "argmax", "rank", "delta", "seq_logp", "seq_count", "acc")
-
-    def __init__(self):
-        for k in self.__slots__:
-            setattr(self, k, None)
 
 
 SCORE_OUTPUTS = ("lse", "logp", "entropy", "argmax", "rank", "delta", "seq_logp", "seq_count")
@@ -488,7 +574,7 @@ SCORE_OUTPUTS = ("lse", "logp", "entropy", "argmax", "rank", "delta", "seq_logp"
 
 def score_workspace(rows, device):
     """A cg_score_rows workspace for up to ``rows`` rows (8-byte aligned)."""
-    return torch.empty(int(L.lib.cg_score_workspace(int(rows))) // 8 + 1, dtype=torch.float64, device=device)
+    return _alloc_ws(L.lib.cg_score_workspace(int(rows)), device, "f64")
 
 
 def score_rows(logits, targets=None, *, V=None, ignore_index=0, smoothing=0.0, sel=None, T=0, acc=None,
@@ -499,51 +585,33 @@ def score_rows(logits, targets=None, *, V=None, ignore_index=0, smoothing=0.0, s
     fp64 [rows / T] and ``seq_count`` int32 with ``T`` rows per sequence, and ``acc``: the fp64 [4]
     accumulator the launch added to (nll sum, smoothed sum, valid rows, top-1 hits)."""
     L.require_device(logits, "score_rows")
-    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[0] and logits.stride(1) != 1):
-        raise ValueError("score_rows: logits is fp32 [rows][ld] with contiguous rows")
-    unknown = set(want) - set(SCORE_OUTPUTS)
-    if unknown:
-        raise ValueError(f"score_rows: unknown outputs {sorted(unknown)}")
+    ldl = _row_matrix(logits, "score_rows: logits", width=V)
+    _check_want("score_rows", want, SCORE_OUTPUTS)
     rows = logits.shape[0]
     V = logits.shape[1] if V is None else int(V)
     dev = logits.device
     d = L.ScoreDesc()
-    d.logits, d.ldl, d.rows, d.V = logits.data_ptr(), logits.stride(0) if rows else V, rows, V
+    d.logits, d.ldl, d.rows, d.V = logits.data_ptr(), ldl, rows, V
     if targets is not None:
-        L.require_device(targets, "score_rows")
-        targets = targets.reshape(-1).to(torch.int64).contiguous()
-        if targets.numel() != rows:
-            raise ValueError("score_rows: one target per row")
+        targets = _per_row(targets, "score_rows", "target", torch.int64, rows)
         d.targets = targets.data_ptr()
     d.ignore_index, d.smoothing, d.T = int(ignore_index), float(smoothing), int(T)
     res = ScoreResult()
-    for name, dt in (("lse", torch.float32), ("logp", torch.float32), ("entropy", torch.float32),
-                     ("argmax", torch.int32), ("rank", torch.int32)):
-        if name in want:
-            t = torch.empty(rows, dtype=dt, device=dev)
-            setattr(res, name, t)
-            setattr(d, name, t.data_ptr())
     if "delta" in want or sel is not None:
         if sel is None or sel.dtype != torch.int32 or not sel.is_cuda or not sel.is_contiguous() or sel.numel() < 1:
             raise ValueError("score_rows: delta needs sel, a contiguous device int32 class list")
         res.delta = torch.empty(rows, sel.numel(), dtype=torch.float32, device=dev)
         d.sel, d.n_sel, d.delta, d.ld_delta = sel.data_ptr(), sel.numel(), res.delta.data_ptr(), sel.numel()
-    if "seq_logp" in want or "seq_count" in want:
-        if T <= 0 or rows % T:
-            raise ValueError("score_rows: sequence sums need T > 0 dividing the row count")
-        if "seq_logp" in want:
-            res.seq_logp = torch.empty(rows // T, dtype=torch.float64, device=dev)
-            d.seq_logp = res.seq_logp.data_ptr()
-        if "seq_count" in want:
-            res.seq_count = torch.empty(rows // T, dtype=torch.int32, device=dev)
-            d.seq_count = res.seq_count.data_ptr()
+    if ("seq_logp" in want or "seq_count" in want) and (T <= 0 or rows % T):
+        raise ValueError("score_rows: sequence sums need T > 0 dividing the row count")
+    seqs = rows // T if T > 0 else 0
+    _alloc_outputs(d, res, want, dev, (
+        ("lse", rows, torch.float32), ("logp", rows, torch.float32), ("entropy", rows, torch.float32),
+        ("argmax", rows, torch.int32), ("rank", rows, torch.int32),
+        ("seq_logp", seqs, torch.float64), ("seq_count", seqs, torch.int32)))
     if acc is not None:
-        if acc.dtype != torch.float64 or acc.numel() != 4 or not acc.is_cuda or not acc.is_contiguous():
-            raise ValueError("score_rows: acc is a contiguous device fp64 [4]")
-        res.acc = acc
-        d.acc = acc.data_ptr()
-    ws = workspace if workspace is not None else score_workspace(rows, dev)
-    d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+        res.acc, d.acc = acc, _dev_tensor(acc, torch.float64, 4, "score_rows: acc")
+    _set_ws(d, _pick_ws(workspace, dev, "f64", False, L.lib.cg_score_workspace, rows))
     L.check(L.lib.cg_score_rows(C.byref(d), L.stream_ptr(dev)), "cg_score_rows")
     return res
 
@@ -559,38 +627,27 @@ def attr_seed(logits, y, w=None, *, V=None, mode="logprob", pad_to=None, split=F
     ``y`` int64 [rows] and ``w`` fp32 [rows] (None = 1) live on the device; a row with y outside
     [0, V) or w == 0 is all zero, and so are the pad columns."""
     L.require_device(logits, "attr_seed")
-    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[0] and logits.stride(1) != 1):
-        raise ValueError("attr_seed: logits is fp32 [rows][ld] with contiguous rows")
+    ldl = _row_matrix(logits, "attr_seed: logits", width=V)
     if mode not in ATTR_MODES:
         raise ValueError(f"attr_seed: mode is one of {sorted(ATTR_MODES)}")
     rows = logits.shape[0]
     V = logits.shape[1] if V is None else int(V)
     dev = logits.device
-    L.require_device(y, "attr_seed")
-    y = y.reshape(-1).to(torch.int64).contiguous()
-    if y.numel() != rows:
-        raise ValueError("attr_seed: one class per row")
+    y = _per_row(y, "attr_seed", "class", torch.int64, rows)
     if w is not None:
-        L.require_device(w, "attr_seed")
-        w = w.reshape(-1).to(torch.float32).contiguous()
-        if w.numel() != rows:
-            raise ValueError("attr_seed: one weight per row")
+        w = _per_row(w, "attr_seed", "weight", torch.float32, rows)
     ldd = int(pad_to) if pad_to else (2 * V if split else V)
     out = torch.empty(rows, ldd, dtype=torch.bfloat16 if split else torch.float32, device=dev)
-    L.check(L.lib.cg_attr_seed(logits.data_ptr(), logits.stride(0) if rows else V, y.data_ptr(), _p(w), rows, V,
+    L.check(L.lib.cg_attr_seed(logits.data_ptr(), ldl, y.data_ptr(), _p(w), rows, V,
                                ATTR_MODES[mode], L.CG_BF16X2 if split else L.CG_F32, out.data_ptr(), ldd,
                                L.stream_ptr(dev)), "cg_attr_seed")
     return out
 
 
-class AttrResult:
+class AttrResult(_Result):
     """Device tensors of one attr_reduce / Engine.input_grad call; an output that was not asked for
     is None."""
     __slots__ = ("gxt", "gxi", "gnorm", "dx0")
-
-    def __init__(self):
-        for k in self.__slots__:
-            setattr(self, k, None)
 
 
 ATTR_OUTPUTS = ("gxt", "gxi", "gnorm")
@@ -602,26 +659,20 @@ def attr_reduce(g, idx, tok_emb=None, x0=None, *, want=ATTR_OUTPUTS):
     |g|, fp32 [rows] each, for the outputs named in ``want``.  ``idx`` int64 [rows], ``tok_emb`` fp32
     [V][>= d] and ``x0`` fp32 [rows][>= d] live on the device."""
     L.require_device(g, "attr_reduce")
-    unknown = set(want) - set(ATTR_OUTPUTS)
-    if unknown:
-        raise ValueError(f"attr_reduce: unknown outputs {sorted(unknown)}")
-    for name, t in (("g", g), ("tok_emb", tok_emb), ("x0", x0)):
-        if t is not None and (t.dim() != 2 or t.dtype != torch.float32 or (t.shape[0] and t.stride(1) != 1)):
-            raise ValueError(f"attr_reduce: {name} is fp32 [rows][ld] with contiguous rows")
+    _check_want("attr_reduce", want, ATTR_OUTPUTS)
+    ldg = _row_matrix(g, "attr_reduce: g")
+    for name, t in (("tok_emb", tok_emb), ("x0", x0)):  # their strides below: x0's follows g's row count
+        if t is not None:
+            _row_matrix(t, f"attr_reduce: {name}")
     rows, d = g.shape
-    L.require_device(idx, "attr_reduce")
-    idx = idx.reshape(-1).to(torch.int64).contiguous()
-    if idx.numel() != rows:
-        raise ValueError("attr_reduce: one token id per row")
+    idx = _per_row(idx, "attr_reduce", "token id", torch.int64, rows)
     if "gxt" in want and (tok_emb is None or tok_emb.shape[1] != d):
         raise ValueError("attr_reduce: gxt needs tok_emb [V][d]")
     if "gxi" in want and (x0 is None or tuple(x0.shape) != (rows, d)):
         raise ValueError("attr_reduce: gxi needs x0 [rows][d]")
     res = AttrResult()
-    for name in ATTR_OUTPUTS:
-        if name in want:
-            setattr(res, name, torch.empty(rows, dtype=torch.float32, device=g.device))
-    L.check(L.lib.cg_attr_reduce(g.data_ptr(), g.stride(0) if rows else d, idx.data_ptr(), _p(tok_emb),
+    _alloc_outputs(None, res, want, g.device, [(name, rows, torch.float32) for name in ATTR_OUTPUTS])
+    L.check(L.lib.cg_attr_reduce(g.data_ptr(), ldg, idx.data_ptr(), _p(tok_emb),
                                  tok_emb.stride(0) if tok_emb is not None else 0,
                                  tok_emb.shape[0] if tok_emb is not None else 0, _p(x0),
                                  x0.stride(0) if x0 is not None and rows else d, rows, d, _p(res.gxt), _p(res.gxi),
@@ -690,13 +741,7 @@ def pool_hidden(hidden, idx, mode, content_ids=(), pad_id=0):
     if hidden.stride(2) != 1 or hidden.stride(0) != T * hidden.stride(1):
         hidden = hidden.contiguous()
     idx = idx.to(device=hidden.device, dtype=torch.int64).contiguous()
-    words = [0] * 8
-    for t in content_ids:
-        t = int(t)
-        if not 0 <= t < 256:
-            raise ValueError("content ids must be in [0, 256)")
-        words[t >> 5] |= 1 << (t & 31)
-    mask = (C.c_uint32 * 8)(*words)
+    mask = _id_mask(content_ids, "content ids")
     out = torch.empty(B, d, dtype=torch.float32, device=hidden.device)
     L.check(L.lib.cg_pool_hidden(_dt(hidden), hidden.data_ptr(), hidden.stride(1), idx.data_ptr(), B, T, d,
                                  int(pad_id), POOL_MODES[mode], mask, out.data_ptr(),
@@ -712,7 +757,7 @@ def colsum(x, out=None, accumulate=False):
         out = torch.empty(cols, dtype=torch.float32, device=x.device)
     ws = torch.empty(int(L.lib.cg_colsum_workspace(rows, cols)) // 4 + 1, dtype=torch.float32, device=x.device)
     L.check(L.lib.cg_colsum(_dt(x), x.data_ptr(), x.stride(0), rows, cols, out.data_ptr(), int(bool(accumulate)),
-                            ws.data_ptr(), ws.numel() * 4, L.stream_ptr(x.device)), "cg_colsum")
+                            ws.data_ptr(), _nbytes(ws), L.stream_ptr(x.device)), "cg_colsum")
     return out
 
 
@@ -779,11 +824,11 @@ def gemm_dw_grouped(products, *, tile_m=0, ksplit=1, max_wg=0, workspace=None):
         ws = workspace
         if ws is None:
             ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=products[0][0].device)
-        elif ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() * 4 < nbytes:
+        elif ws.dtype != torch.float32 or not ws.is_contiguous() or _nbytes(ws) < nbytes:
             raise ValueError(f"gemm_dw_grouped: workspace must be contiguous fp32 of at least {nbytes} bytes")
         else:
             L.require_device(ws, "gemm_dw_grouped")
-        g.workspace, g.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        _set_ws(g, ws)
     L.check(L.lib.cg_gemm_dw_grouped(C.byref(g), L.stream_ptr(products[0][0].device)), "cg_gemm_dw_grouped")
     return ws
 
@@ -837,27 +882,27 @@ def window_pool(hidden, window, stride, dst_row, out):
     return out
 
 
-class KMeansStep:
+class KMeansStep(_Result):
     """Outputs of kmeans_step; an output that was not asked for is None."""
     __slots__ = ("labels", "dist2", "sums", "counts", "inertia")
-
-    def __init__(self, labels=None, dist2=None, sums=None, counts=None, inertia=None):
-        self.labels, self.dist2, self.sums, self.counts, self.inertia = labels, dist2, sums, counts, inertia
 
 
 def kmeans_step(x, centers, *, want_dist2=True, want_stats=True, want_inertia=True, workspace=None):
     """One E-step of Lloyd's algorithm with the M-step's statistics (cg_kmeans_step): labels int32
     (n), dist2 fp32 (n), sums fp64 (k, d), counts int64 (k), inertia fp64 scalar tensor.  x fp32
     (n, d) and centers fp32 (k, d) may have padded rows.  workspace: a uint8 buffer to reuse."""
-    for t in (x, centers):
+    ld = []
+    for name, t in (("x", x), ("centers", centers)):
         L.require_device(t, "kmeans_step")
-        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-            raise ValueError("kmeans_step: fp32 matrices with unit column stride")
+        ld.append(_row_matrix(t, f"kmeans_step: {name}", loose=True))
     n, d = x.shape
     k = centers.shape[0]
     if centers.shape[1] != d:
         raise ValueError("kmeans_step: points and centres differ in width")
     dev = x.device
+    p = L.KMeansDesc()
+    p.x, p.ldx, p.n, p.d = x.data_ptr(), ld[0], n, d
+    p.centers, p.ldc, p.k = centers.data_ptr(), ld[1], k
     r = KMeansStep(labels=torch.empty(n, dtype=torch.int32, device=dev))
     if want_dist2:
         r.dist2 = torch.empty(n, dtype=torch.float32, device=dev)
@@ -866,15 +911,8 @@ def kmeans_step(x, centers, *, want_dist2=True, want_stats=True, want_inertia=Tr
         r.counts = torch.zeros(k, dtype=torch.int64, device=dev)
     if want_inertia:
         r.inertia = torch.zeros((), dtype=torch.float64, device=dev)
-    need = int(L.lib.cg_kmeans_workspace(n, d, k))
-    ws = workspace
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    p = L.KMeansDesc()
-    p.x, p.ldx, p.n, p.d = x.data_ptr(), x.stride(0) if n > 1 else max(d, x.stride(0)), n, d
-    p.centers, p.ldc, p.k = centers.data_ptr(), centers.stride(0) if k > 1 else max(d, centers.stride(0)), k
     p.labels, p.dist2, p.sums, p.counts, p.inertia = _p(r.labels), _p(r.dist2), _p(r.sums), _p(r.counts), _p(r.inertia)
-    p.workspace, p.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    _set_ws(p, _pick_ws(workspace, dev, "u8", True, L.lib.cg_kmeans_workspace, n, d, k))
     L.check(L.lib.cg_kmeans_step(C.byref(p), L.stream_ptr(dev)), "cg_kmeans_step")
     return r
 
@@ -885,20 +923,15 @@ class TermCE:
     __slots__ = ("loss", "sums", "x", "W", "bias", "labels", "class_w", "ignore_index", "workspace")
 
 
-def _rows2d(t, what, dtypes):
-    if t.dtype not in dtypes or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"{what}: a 2-D {' / '.join(str(d) for d in dtypes)} matrix with unit column stride")
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
-
-
 def _term_ce_desc(st: TermCE):
     x, W = st.x, st.W
     p = L.TermCeDesc()
-    p.x_dtype, p.x, p.ldx = _dt(x), x.data_ptr(), _rows2d(x, "term_ce: x", (torch.float32, torch.bfloat16))
+    p.x_dtype, p.x = _dt(x), x.data_ptr()
+    p.ldx = _row_matrix(x, "term_ce: x", (torch.float32, torch.bfloat16), loose=True)
     p.rows, p.d, p.C = x.shape[0], x.shape[1], W.shape[0]
-    p.W, p.ldw = W.data_ptr(), _rows2d(W, "term_ce: W", (torch.float32,))
+    p.W, p.ldw = W.data_ptr(), _row_matrix(W, "term_ce: W", loose=True)
     p.bias, p.labels, p.ignore_index, p.class_w = st.bias.data_ptr(), st.labels.data_ptr(), st.ignore_index, _p(st.class_w)
-    p.workspace, p.ws_bytes = st.workspace.data_ptr(), st.workspace.numel() * st.workspace.element_size()
+    _set_ws(p, st.workspace)
     return p
 
 
@@ -920,16 +953,13 @@ def term_ce_fwd(x, W, bias, labels, *, class_w=None, ignore_index=-100, workspac
     st = TermCE()
     st.x, st.W = x, W
     st.bias = bias.to(torch.float32).contiguous()
-    st.labels = labels.reshape(-1).to(torch.int64).contiguous()
+    st.labels = labels.reshape(-1).to(torch.int64).contiguous()  # device and count checked above
     st.class_w = None if class_w is None else class_w.to(torch.float32).contiguous()
     st.ignore_index = int(ignore_index)
     st.loss = torch.empty((), dtype=torch.float32, device=dev)
     st.sums = torch.empty(2, dtype=torch.float32, device=dev)
-    need = int(L.lib.cg_term_ce_workspace(rows, d, min(nc, L.TERM_CE_MAX_CLASSES)))
-    ws = workspace
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    st.workspace = ws
+    st.workspace = _pick_ws(workspace, dev, "u8", True, L.lib.cg_term_ce_workspace, rows, d,
+                            min(nc, L.TERM_CE_MAX_CLASSES))
     p = _term_ce_desc(st)
     p.loss, p.sums = st.loss.data_ptr(), st.sums.data_ptr()
     L.check(L.lib.cg_term_ce_fwd(C.byref(p), L.stream_ptr(dev)), "cg_term_ce_fwd")
@@ -970,7 +1000,7 @@ def term_ce_bwd(st: TermCE, *, scale=1.0, scale_dev=None, dW=None, db=None, dx=N
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError("term_ce_bwd: db must be contiguous fp32")
         else:
-            setattr(p, "ld" + name.lower(), _rows2d(t, f"term_ce_bwd: {name}", (torch.float32,)))
+            setattr(p, "ld" + name.lower(), _row_matrix(t, f"term_ce_bwd: {name}", loose=True))
     L.check(L.lib.cg_term_ce_bwd(C.byref(p), L.stream_ptr(dev)), "cg_term_ce_bwd")
     return outs["dW"], outs["db"], outs["dx"]
 
@@ -1027,13 +1057,9 @@ def ngram_totals(tables: NgramTables):
     return tables
 
 
-class NgramNll:
+class NgramNll(_Result):
     """Device tensors of one ngram_nll call; an output that was not asked for is None."""
     __slots__ = ("tok_tri", "row_sums", "row_count", "acc")
-
-    def __init__(self):
-        for k in self.__slots__:
-            setattr(self, k, None)
 
 
 NGRAM_OUTPUTS = ("tok_tri", "row_sums", "row_count")
@@ -1044,9 +1070,7 @@ def ngram_nll(tables: NgramTables, x, y, alpha=0.01, *, acc=None, want=("row_sum
     the reference): ``tok_tri`` fp32 [B][T], ``row_sums`` fp64 [B][4] (uniform, unigram, bigram,
     trigram), ``row_count`` int32 [B], and ``acc``: the fp64 [5] accumulator the launch added to."""
     x, y = _xy(x, y, "ngram_nll")
-    unknown = set(want) - set(NGRAM_OUTPUTS)
-    if unknown:
-        raise ValueError(f"ngram_nll: unknown outputs {sorted(unknown)}")
+    _check_want("ngram_nll", want, NGRAM_OUTPUTS)
     if tables.uni_total is None:
         raise ValueError("ngram_nll: call ngram_totals after the last ngram_count")
     B, T = x.shape
@@ -1058,31 +1082,18 @@ def ngram_nll(tables: NgramTables, x, y, alpha=0.01, *, acc=None, want=("row_sum
     for name in ("uni", "bi", "tri", "uni_total", "bi_total", "tri_total"):
         setattr(d, name, getattr(tables, name).data_ptr())
     res = NgramNll()
-    for name, shape, dt in (("tok_tri", (B, T), torch.float32), ("row_sums", (B, 4), torch.float64),
-                            ("row_count", (B,), torch.int32)):
-        if name in want:
-            t = torch.empty(shape, dtype=dt, device=dev)
-            setattr(res, name, t)
-            setattr(d, name, t.data_ptr())
-    if acc is not None:
-        if acc.dtype != torch.float64 or acc.numel() != 5 or not acc.is_cuda or not acc.is_contiguous():
-            raise ValueError("ngram_nll: acc is a contiguous device fp64 [5]")
-        res.acc = acc
-        d.acc = acc.data_ptr()
-        ws = workspace if workspace is not None else torch.empty(
-            int(L.lib.cg_ngram_nll_workspace(B)) // 8 + 1, dtype=torch.float64, device=dev)
-        d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    _alloc_outputs(d, res, want, dev, (("tok_tri", (B, T), torch.float32), ("row_sums", (B, 4), torch.float64),
+                                       ("row_count", B, torch.int32)))
+    if acc is not None:  # the workspace holds the accumulator's partials: set only with one
+        res.acc, d.acc = acc, _dev_tensor(acc, torch.float64, 5, "ngram_nll: acc")
+        _set_ws(d, _pick_ws(workspace, dev, "f64", False, L.lib.cg_ngram_nll_workspace, B))
     L.check(L.lib.cg_ngram_nll(C.byref(d), L.stream_ptr(dev)), "cg_ngram_nll")
     return res
 
 
-class DiagResult:
+class DiagResult(_Result):
     """Device tensors of one diag_rows call; an output that was not asked for is None."""
     __slots__ = ("nll", "segpos", "conf", "row_nll", "row_count", "slices", "calib", "brier_acc")
-
-    def __init__(self):
-        for k in self.__slots__:
-            setattr(self, k, None)
 
 
 DIAG_OUTPUTS = ("nll", "segpos", "conf", "row_nll", "row_count")
@@ -1090,13 +1101,7 @@ DIAG_OUTPUTS = ("nll", "segpos", "conf", "row_nll", "row_count")
 
 def diag_workspace(B, device):
     """A cg_diag_rows workspace for up to ``B`` rows (8-byte aligned)."""
-    return torch.empty(int(L.lib.cg_diag_workspace(int(B))) // 8 + 1, dtype=torch.float64, device=device)
-
-
-def _dev_tensor(t, dtype, numel, what):
-    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError(f"{what} is a contiguous device {dtype} of {numel} elements")
-    return t.data_ptr()
+    return _alloc_ws(L.lib.cg_diag_workspace(int(B)), device, "f64")
 
 
 def diag_rows(logits, x, y, *, V=None, pad_id=0, sep_id=3, row_flag=None, tok_class=None, edges=None, slices=None,
@@ -1110,16 +1115,14 @@ def diag_rows(logits, x, y, *, V=None, pad_id=0, sep_id=3, row_flag=None, tok_cl
     L.require_device(logits, "diag_rows")
     x, y = _xy(x, y, "diag_rows")
     B, T = x.shape
-    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] != B * T or \
-            (logits.shape[0] and logits.stride(1) != 1):
-        raise ValueError("diag_rows: logits is fp32 [B*T][ld] with contiguous rows")
-    unknown = set(want) - set(DIAG_OUTPUTS)
-    if unknown:
-        raise ValueError(f"diag_rows: unknown outputs {sorted(unknown)}")
+    ldl = _row_matrix(logits, "diag_rows: logits", width=V)
+    if logits.shape[0] != B * T:
+        raise ValueError("diag_rows: logits has one row per position of x, [B*T][ld]")
+    _check_want("diag_rows", want, DIAG_OUTPUTS)
     V = logits.shape[1] if V is None else int(V)
     dev = logits.device
     d = L.DiagDesc()
-    d.logits, d.ldl = logits.data_ptr(), logits.stride(0) if B * T else V
+    d.logits, d.ldl = logits.data_ptr(), ldl
     d.x, d.y, d.B, d.T, d.V, d.pad_id, d.sep_id = x.data_ptr(), y.data_ptr(), B, T, V, int(pad_id), int(sep_id)
     if row_flag is not None:
         d.row_flag = _dev_tensor(row_flag, torch.uint8, B, "diag_rows: row_flag")
@@ -1138,27 +1141,18 @@ def diag_rows(logits, x, y, *, V=None, pad_id=0, sep_id=3, row_flag=None, tok_cl
     if brier_acc is not None:
         d.brier_acc = _dev_tensor(brier_acc, torch.float64, 2, "diag_rows: brier_acc")
     res.slices, res.calib, res.brier_acc = slices, calib, brier_acc
-    for name, shape, dt in (("nll", (B, T), torch.float32), ("segpos", (B, T), torch.int32),
-                            ("conf", (B, T), torch.float32), ("row_nll", (B,), torch.float64),
-                            ("row_count", (B,), torch.int32)):
-        if name in want:
-            t = torch.empty(shape, dtype=dt, device=dev)
-            setattr(res, name, t)
-            setattr(d, name, t.data_ptr())
-    if slices is not None or calib is not None or brier_acc is not None:
-        ws = workspace if workspace is not None else diag_workspace(B, dev)
-        d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    _alloc_outputs(d, res, want, dev, (
+        ("nll", (B, T), torch.float32), ("segpos", (B, T), torch.int32), ("conf", (B, T), torch.float32),
+        ("row_nll", B, torch.float64), ("row_count", B, torch.int32)))
+    if slices is not None or calib is not None or brier_acc is not None:  # a workspace only with an accumulator
+        _set_ws(d, _pick_ws(workspace, dev, "f64", False, L.lib.cg_diag_workspace, B))
     L.check(L.lib.cg_diag_rows(C.byref(d), L.stream_ptr(dev)), "cg_diag_rows")
     return res
 
 
-class AttnStatsResult:
+class AttnStatsResult(_Result):
     """Device tensors of one attn_stats call; an output that was not asked for is None."""
     __slots__ = ("rows", "nvis", "received", "head_acc", "n_rows")
-
-    def __init__(self):
-        for k in self.__slots__:
-            setattr(self, k, None)
 
 
 ATTN_STATS_OUTPUTS = ("rows", "nvis", "received")
@@ -1166,17 +1160,14 @@ ATTN_STATS_OUTPUTS = ("rows", "nvis", "received")
 
 def attn_stats_workspace(B, T, H, device):
     """A cg_attn_stats workspace for (B, T, H) (8-byte aligned)."""
-    return torch.empty(int(L.lib.cg_attn_stats_workspace(int(B), int(T), int(H))) // 8 + 1, dtype=torch.float64,
-                       device=device)
+    return _alloc_ws(L.lib.cg_attn_stats_workspace(int(B), int(T), int(H)), device, "f64")
 
 
 def attn_stats_fill(d, res, B, T, H, dev, *, idx=None, pad_id=-1, tok_class=None, row_keep=None,
                     want=ATTN_STATS_OUTPUTS, head_acc=None, n_rows=None, workspace=None):
     """The fields of an AttnStatsDesc a caller chooses (token ids, classes, row filter, outputs,
     workspace), shared by attn_stats and Engine.attn_stats; returns the tensors to keep alive."""
-    unknown = set(want) - set(ATTN_STATS_OUTPUTS)
-    if unknown:
-        raise ValueError(f"attn_stats: unknown outputs {sorted(unknown)}")
+    _check_want("attn_stats", want, ATTN_STATS_OUTPUTS)
     keep = []
     if idx is not None:
         idx = idx.to(device=dev, dtype=torch.int64).contiguous()
@@ -1189,19 +1180,15 @@ def attn_stats_fill(d, res, B, T, H, dev, *, idx=None, pad_id=-1, tok_class=None
         row_keep = row_keep.to(device=dev, dtype=torch.uint8).contiguous()
         d.row_keep = _dev_tensor(row_keep, torch.uint8, B * T, "attn_stats: row_keep")
         keep.append(row_keep)
-    for name, shape, dt in (("rows", (B, H, T, L.AS_NSTAT), torch.float32), ("nvis", (B, T), torch.int32),
-                            ("received", (B, H, T), torch.float32)):
-        if name in want:
-            t = torch.empty(shape, dtype=dt, device=dev)
-            setattr(res, name, t)
-            setattr(d, name, t.data_ptr())
+    _alloc_outputs(d, res, want, dev, (("rows", (B, H, T, L.AS_NSTAT), torch.float32), ("nvis", (B, T), torch.int32),
+                                       ("received", (B, H, T), torch.float32)))
     if head_acc is not None:
         d.head_acc = _dev_tensor(head_acc, torch.float64, H * L.AS_NSTAT, "attn_stats: head_acc")
     if n_rows is not None:
         d.n_rows = _dev_tensor(n_rows, torch.float64, 1, "attn_stats: n_rows")
     res.head_acc, res.n_rows = head_acc, n_rows
-    ws = workspace if workspace is not None else attn_stats_workspace(B, T, H, dev)
-    d.workspace, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    ws = _pick_ws(workspace, dev, "f64", False, L.lib.cg_attn_stats_workspace, B, T, H)
+    _set_ws(d, ws)
     keep.append(ws)
     return keep
 
@@ -1215,6 +1202,7 @@ def attn_stats(qkv, segstart, B, T, H, KV, hd, *, window=0, idx=None, pad_id=-1,
     written.  ``idx`` int64 [B][T] with ``pad_id`` drops PAD rows and, with ``tok_class`` uint8 [V],
     gives the key classes; ``row_keep`` uint8 [B][T] filters the query rows."""
     L.require_device(qkv, "attn_stats")
+    # not _row_matrix: any dtype _dt takes, and "empty" is numel() == 0 with the stride (H + 2 KV) hd
     if qkv.dim() != 2 or qkv.shape[0] != B * T or (qkv.numel() and qkv.stride(1) != 1):
         raise ValueError("attn_stats: qkv is [B*T][(H + 2 KV) hd] with contiguous rows")
     dev = qkv.device
@@ -1231,7 +1219,7 @@ def attn_stats(qkv, segstart, B, T, H, KV, hd, *, window=0, idx=None, pad_id=-1,
 
 
 # ---------------------------------------------------------------------------- structural regression probes
-SHAPE_TARGETS = 14  # CG_SHAPE_TARGETS
+SHAPE_TARGETS = L.SHAPE_TARGETS
 
 
 def _rows_view(t, what):
@@ -1266,6 +1254,7 @@ def shape_targets(idx, codon_of, out=None):
     if len(tab) > 256:
         raise ValueError("shape_targets: at most 256 ids")
     y = torch.zeros(B * T, SHAPE_TARGETS, dtype=torch.float32, device=idx.device) if out is None else out
+    # not _row_matrix: numel() decides "empty", and the stride is raised to the width for every row count
     if y.dtype != torch.float32 or y.dim() != 2 or y.shape[0] != B * T or (y.numel() and y.stride(1) != 1):
         raise ValueError("shape_targets: out must be fp32 (B*T, >= 14) with unit column stride")
     ldy = max(int(y.stride(0)), y.shape[1]) if y.shape[1] else 0
@@ -1278,8 +1267,7 @@ def shape_targets(idx, codon_of, out=None):
 
 def gram_workspace(rows, d, m, G, device):
     """A cg_gram_accum workspace for these sizes (a uint8 tensor)."""
-    need = int(L.lib.cg_gram_workspace(int(rows), int(d), int(m), int(G)))
-    return torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+    return _alloc_ws(L.lib.cg_gram_workspace(int(rows), int(d), int(m), int(G)), device, "u8_256")
 
 
 def gram_accum(h, y, grp, G, gram=None, *, m=None, accumulate=False, workspace=None):
@@ -1319,13 +1307,10 @@ def gram_accum(h, y, grp, G, gram=None, *, m=None, accumulate=False, workspace=N
     if (gram.dtype != torch.float64 or gram.dim() != 3 or tuple(gram.shape) != (G, P, P) or gram.stride(2) != 1
             or (G > 1 and gram.stride(0) != P * gram.stride(1))):
         raise ValueError("gram_accum: gram must be fp64 (G, P, P) with evenly spaced rows")
-    need = int(L.lib.cg_gram_workspace(rows, d, m, G))
-    ws = workspace
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = gram_workspace(rows, d, m, G, dev)
+    ws = _pick_ws(workspace, dev, "u8_256", True, L.lib.cg_gram_workspace, rows, d, m, G)
     L.check(L.lib.cg_gram_accum(_dt(h), h.data_ptr(), ldh, d, _p(yk), ldy, m, grp.data_ptr(), rows, G,
                                 1 if accumulate else 0, gram.data_ptr(), max(int(gram.stride(1)), P), ws.data_ptr(),
-                                ws.numel() * ws.element_size(), L.stream_ptr(dev)), "cg_gram_accum")
+                                _nbytes(ws), L.stream_ptr(dev)), "cg_gram_accum")
     return gram
 
 
@@ -1406,13 +1391,9 @@ def ngram_index_build(index: NgramIndex, seq_lo: int = 0, seq_hi=None) -> NgramI
     return index
 
 
-class NgramCoverage:
+class NgramCoverage(_Result):
     """Device tensors of one ngram_coverage call; an output that was not asked for is None."""
     __slots__ = ("hit", "n_hit", "covered")
-
-    def __init__(self):
-        for k in self.__slots__:
-            setattr(self, k, None)
 
 
 COVERAGE_OUTPUTS = ("hit", "n_hit", "covered")
@@ -1423,9 +1404,7 @@ def ngram_coverage(index: NgramIndex, qsym, qoffsets, want=("n_hit", "covered"))
     built index: ``hit`` uint8 like qsym (1 at the starts of windows the index holds), ``n_hit`` int32
     [n_q], ``covered`` int32 [n_q] (positions inside at least one hit window).  A query longer than
     16384 symbols raises ValueError (CG_EUNSUPPORTED)."""
-    unknown = set(want) - set(COVERAGE_OUTPUTS)
-    if unknown:
-        raise ValueError(f"ngram_coverage: unknown outputs {sorted(unknown)}")
+    _check_want("ngram_coverage", want, COVERAGE_OUTPUTS)
     qsym, qoff, host = _seq_set(qsym, qoffsets, "ngram_coverage")
     n_q = int(host.size - 1)
     dev = qsym.device
@@ -1435,11 +1414,7 @@ def ngram_coverage(index: NgramIndex, qsym, qoffsets, want=("n_hit", "covered"))
     d.qsym, d.n_qsym, d.qoffsets, d.n_q = qsym.data_ptr(), qsym.numel(), qoff.data_ptr(), n_q
     d.max_qlen = int(np.diff(host).max()) if n_q else 0
     res = NgramCoverage()
-    for name, t in (("hit", lambda: torch.zeros(qsym.numel(), dtype=torch.uint8, device=dev)),
-                    ("n_hit", lambda: torch.empty(n_q, dtype=torch.int32, device=dev)),
-                    ("covered", lambda: torch.empty(n_q, dtype=torch.int32, device=dev))):
-        if name in want:
-            setattr(res, name, t())
-            setattr(d, name, getattr(res, name).data_ptr())
+    _alloc_outputs(d, res, want, dev, (("hit", qsym.numel(), torch.uint8), ("n_hit", n_q, torch.int32),
+                                       ("covered", n_q, torch.int32)), zero=("hit",))
     L.check(L.lib.cg_ngram_coverage(C.byref(d), L.stream_ptr(dev)), "cg_ngram_coverage")
     return res

@@ -32,12 +32,9 @@ def test_ctypes_struct_mirrors_match_the_library():
     (cg_struct_bytes), so a field added on one side only fails here, not as a misread argument."""
     import ctypes
     from codonlm_amd import _lib as L
-    mirrors = {"cg_gemm_desc": L.GemmDesc, "cg_dw_product": L.DwProduct, "cg_dw_group": L.DwGroup,
-               "cg_reduce_job": L.ReduceJob, "cg_reduce_batch": L.ReduceBatch,
-               "cg_transpose_item": L.TransposeItem, "cg_transpose_batch": L.TransposeBatch,
-               "cg_adamw_segment": L.AdamwSegment, "cg_model_cfg": L.ModelCfg,
-               "cg_param_entry": L.ParamEntry, "cg_model": L.Model, "cg_model_opts": L.ModelOpts}
-    for name, cls in mirrors.items():
+    from header_reader import read_header
+    assert set(L.STRUCTS) == set(read_header()["structs"]) and len(L.STRUCTS) >= 25
+    for name, cls in L.STRUCTS.items():
         assert L.lib.cg_struct_bytes(name.encode()) == ctypes.sizeof(cls), name
     assert L.lib.cg_struct_bytes(b"nope") == 0
 

@@ -1,6 +1,8 @@
-"""Run every op that uses the shared helpers of csrc/common.h (wave reductions, vector loaders, id
-mask, capped grid) once on seeded inputs, at the smallest shapes that reach each of their paths,
-and save every output to a .npz, so two library builds can be compared bit for bit:
+"""Run the op wrappers of codonlm_amd/ops.py once on seeded inputs, at the smallest shapes that reach
+each path of the shared csrc/common.h helpers (wave reductions, vector loaders, id mask, capped grid)
+and each branch of the wrappers' own helpers (output tables, workspace policies, row-matrix and
+per-row checks, the decode / sample / LayerNorm twins), and save every output to a .npz.  Two library
+builds, or two versions of the Python binding over one library, can then be compared bit for bit:
     CG_LIB_PATH=<lib> python tools/ops_bits_dump.py out.npz"""
 import sys
 from pathlib import Path
@@ -94,6 +96,57 @@ for dt in (torch.bfloat16, torch.float32):  # swiglu: the 8-element vector kerne
     gu, ds = randn(37, 352, dtype=dt), randn(37, 176, dtype=dt)
     put(f"swiglu_fwd.{dt}", ops.swiglu_fwd(gu, 170))
     put(f"swiglu_bwd.{dt}", ops.swiglu_bwd(gu, ds, 170))
+
+x = randn(70, 96)  # LayerNorm forward and its dropout-mask twin
+for name, r in (("ln", ops.layernorm_fwd(x, randn(96), randn(96))),
+                ("ln_mask", ops.layernorm_fwd_mask(x, randn(96), randn(96), 2, 35, 4, 11, 0.1))):
+    for n, t in zip(("y", "mean", "rstd", "mask"), r):
+        put(f"{name}.{n}", t)
+
+a, b = randn(70, 64, dtype=torch.bfloat16), randn(48, 64, dtype=torch.bfloat16)  # gemm workspaces, colsum
+cs = torch.empty(48, device="cuda")
+put("gemm.split_k", ops.gemm(randn(70, 64), randn(48, 64), split_k=2))
+put("gemm.colsum_out.c", ops.gemm(a, b, colsum_out=cs))
+put("gemm.colsum_out.s", cs)
+put("colsum", ops.colsum(randn(300, 50)))
+
+H, KV, hd, Tmax = 4, 2, 16, 40  # one-token attention: a shared position, and one per sequence
+q, cache = randn(3, H * hd), randn(3, Tmax, 2 * KV * hd + 8)
+seg = torch.tensor([0, 5, 17], dtype=torch.int32, device="cuda")
+put("attn_decode", ops.attn_decode(q, cache, 17, H, KV, hd, segstate=seg, window=9))
+pos = torch.tensor([39, -1, 17], dtype=torch.int32, device="cuda")
+put("attn_decode_ragged", ops.attn_decode_ragged(q, cache, pos, H, KV, hd, segstate=seg))
+
+B, T = 2, 70  # attn_stats: every output and both accumulators
+idx = randint(4, V, (B, T))
+idx[:, 30], idx[1, 60:] = 3, 0
+r = ops.attn_stats(randn(B * T, (H + 2 * KV) * hd), ops.segment_starts(idx, 3), B, T, H, KV, hd, window=50, idx=idx,
+                   pad_id=0, tok_class=randint(0, 4, (V,), torch.uint8), row_keep=randint(0, 2, (B, T), torch.uint8),
+                   head_acc=f64(H * L.AS_NSTAT), n_rows=f64(1))
+put_all("attn_stats", r, ops.ATTN_STATS_OUTPUTS + ("head_acc", "n_rows"))
+
+sp = L.SampleParams(V=V, temperature=0.8, topk=5, target_codons=L.INT_MAX, max_codons=L.INT_MAX,  # sample_step twins
+                    max_tokens=L.INT_MAX, seed=7, Tmax=L.INT_MAX)
+tok_class = torch.zeros(V, dtype=torch.uint8, device="cuda")
+sp.tok_class = tok_class.data_ptr()
+z, logp = randn(5, V, scale=3.0), f64(10)
+for name, step in (("sample_step", lambda *a: ops.sample_step(sp, *a)),  # no sets: the same draw, and its log-probs
+                   ("sample_step_plan", lambda *a: ops.sample_step_plan(sp, L.SamplePlan(logp=logp.data_ptr()), *a))):
+    state = torch.zeros(5, 8, dtype=torch.int32, device="cuda")  # cg_gen_state rows: pos0 = pos = 4, stream = row
+    state[:, 0], state[:, 1], state[:, 6], state[:, 7] = 4, 4, -1, torch.arange(5, dtype=torch.int32, device="cuda")
+    nxt, ids = torch.full((5,), -7, device="cuda"), torch.full((5, 8), -7, device="cuda")
+    n_active = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    step(z, state, nxt, ids, n_active)
+    for n, t in (("state", state), ("next_tok", nxt), ("out_ids", ids), ("n_active", n_active)):
+        put(f"{name}.{n}", t)
+put("sample_step_plan.logp", logp)
+
+sym = randint(0, 4, (600,), torch.uint8)  # window index and coverage: hit is zero-filled, the counts are not
+index = ops.ngram_index_build(ops.NgramIndex(sym[:400], [0, 150, 150, 400], 6))
+put_all("ngram_index", index, ("n_unique", "n_dropped"))  # the table's slot order is the insertion race's
+qsym = torch.cat([sym[100:180], sym[400:]])
+put_all("ngram_coverage", ops.ngram_coverage(index, qsym, [0, 80, 83, 280], want=ops.COVERAGE_OUTPUTS),
+        ops.COVERAGE_OUTPUTS)
 
 torch.cuda.synchronize()
 np.savez(sys.argv[1], **out)
